@@ -2,6 +2,12 @@
 """bench.py — faces/sec of SMIRK's per-frame hot path (encode -> FLAME -> render -> generate) at 224x224 on N MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload full|infer256|flame512|train64] [--global-batch G | --batch B_PER_GPU]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps and prints the result line (`value` faces/s, `ms_per_step`); it checks the outputs finite after the
+warm-up and after the timed steps.  `--full` adds everything else described below, each after the timed region: `output_stats`, the idle-queue
+enqueue time of one more step, `roofline` (with its `traffic` counter passes), `cpu_baseline` and, for the default `full` workload on one GPU,
+the other BASELINE configs under `also`.  `--dump-outputs DIR` writes the outputs of the last timed step as DIR/<name>.npy (see dump_outputs).
 
 `--gpus N` with N > 1 launches itself as N ranks (one process per GPU, torch.distributed.run, rendezvous on 127.0.0.1); when the driver
 already started it under torch.distributed.run (RANK / WORLD_SIZE set) it just joins.
@@ -60,6 +66,9 @@ METRIC = {"full": "faces/sec (encode+FLAME+render+generate) @224x224",
           "infer256": "faces/sec (encode+FLAME+render) @224x224",
           "flame512": "faces/sec (FLAME-only: shape,exp,pose,jaw -> 5023 vertices)",
           "train64": "faces/sec (cycle-path training step: render + generate + re-encode + cycle loss + backward + optimiser) @224x224"}
+# --dump-outputs: an output array larger than DUMP_WHOLE_BYTES is written as the same DUMP_FRAMES frames (rows of its batch dimension, drawn once with
+# DUMP_SEED), so a 1024-frame step's images fit under DUMP_LIMIT_BYTES
+DUMP_WHOLE_BYTES, DUMP_FRAMES, DUMP_SEED, DUMP_LIMIT_BYTES = 4 << 20, 16, 20240, 64 << 20
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -108,6 +117,14 @@ def parse_args(argv=None):
     ap.add_argument("--force-collective", action="store_true",
                     help="1 GPU only: create a world-size-1 RCCL group and really enqueue the output all-gather / gradient all-reduce of every step (what a rank of "
                          "the N-GPU job does besides its shard); use with --global-batch 128 to measure the 8-GPU per-rank regime on one MI355X")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: output statistics, the idle-queue enqueue time of one more step, the roofline "
+                         "(instrumented pass + rocprofv3 counter passes), the CPU baseline and, for the default `full` run, the other configs under \"also\".  "
+                         "Without it a run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy (float32 / float64; arrays over %d MB as a fixed "
+                         "seeded sample of %d frames, at most %d MB in all) so that two builds can be compared output for output"
+                         % (DUMP_WHOLE_BYTES >> 20, DUMP_FRAMES, DUMP_LIMIT_BYTES >> 20))
     ap.add_argument("--backend", default="nccl", help=argparse.SUPPRESS)
     ap.add_argument("--plumbing-test", action="store_true", help=argparse.SUPPRESS)   # CPU/gloo stub of the path: tests/test_distributed_cpu.py
     ap.add_argument("--pmc-inner", action="store_true", help=argparse.SUPPRESS)       # the run that rocprofv3 wraps (no JSON line, no baseline)
@@ -179,6 +196,34 @@ def output_stats(out):
         s["vertices_absmax"] = float(out["vertices"].abs().max())
         s["mesh_sane"] = bool(s["vertices_absmax"] < 1.0)          # the head template spans about +-0.15; a random encoder could blow it up
     return s
+
+
+def dump_outputs(out, d):
+    """--dump-outputs: every tensor of the step's output dict (what the caller of the path receives; `_`-prefixed internals left out) as d/<key>.npy, float64
+    where the tensor is float64 or integer, float32 otherwise.  Arrays over DUMP_WHOLE_BYTES keep the DUMP_FRAMES rows of one fixed seeded draw.  `out` is the
+    workload's `last`: the whole last step at the default micro-batch (one pass per step), its last micro-batch when --micro-batch splits the step."""
+    import numpy as np
+    import torch
+    arrays, pick = {}, {}
+    for k in sorted(out):
+        v = out[k]
+        if k.startswith("_") or not torch.is_tensor(v):
+            continue
+        v = v.detach()
+        v = v.double() if v.dtype == torch.float64 or not (v.is_floating_point() or v.dtype == torch.bool) else v.float()
+        if v.dim() > 0 and v.numel() * v.element_size() > DUMP_WHOLE_BYTES and v.shape[0] > DUMP_FRAMES:
+            n = v.shape[0]
+            if n not in pick:
+                pick[n] = torch.from_numpy(np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_FRAMES, replace=False)))
+            v = v[pick[n].to(v.device)]
+        arrays[k] = v.cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total / 2 ** 20:.1f} MB (limit {DUMP_LIMIT_BYTES >> 20} MB)")
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -796,7 +841,7 @@ def run_also(args):
         # (the 128-frame shard's launches are not the 1024-frame table's launches: no traffic for that entry)
         cmd = [sys.executable, os.path.abspath(__file__)] + argv + ["--steps", str(steps), "--warmup", str(warmup), "--traffic", "off" if "--global-batch" in argv else "file",
                                                                     "--cpu-faces", str(cpu_faces if args.cpu_faces > 0 else 0), "--cpu-passes", "3", "--no-also",
-                                                                    "--flame-basis", args.flame_basis]
+                                                                    "--flame-basis", args.flame_basis, "--full"]
         try:
             r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=240, cwd=REPO)
             lines = [ln for ln in r.stdout.decode(errors="replace").splitlines() if ln.startswith("{")]
@@ -836,6 +881,9 @@ def main():
     import torch
     import torch.distributed as dist
     rank, world, local = dist_env()
+    # torch's default generator starts from a different seed in every process; the masking stage keys its random draws on it (smirk_amd/masking.py
+    # _rng), so without this the same command line would mask different pixels from run to run
+    torch.manual_seed(1234 + rank)
     if args.plumbing_test:
         dev = torch.device("cpu")
     else:
@@ -892,22 +940,25 @@ def main():
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
-    stats = {}
+    stats, dumped = {}, None
     if wl.last is not None and not args.plumbing_test:
         assert_finite(wl.last, wl.keys, "after the timed steps")
-        stats = output_stats(wl.last)
+        if args.full:
+            stats = output_stats(wl.last)
+    if args.dump_outputs and rank == 0 and wl.last is not None:
+        dumped = dump_outputs(wl.last, args.dump_outputs)          # before anything below runs the path again
     # host time to enqueue ONE step into an EMPTY launch queue (after the synchronisation above, outside the timed region).  Over the K back-to-back steps of
     # the timed region the launch queue fills and the host blocks on it, so t_host / K measures back-pressure, not enqueue cost (round 4: 33.9 ms in the
     # driver's 20-step run against 2.2 ms in a 5-step run of the same code); both are reported, under names that say which is which.
     t_enq1 = None
-    if not args.plumbing_test and not args.pmc_inner:
+    if args.full and not args.plumbing_test and not args.pmc_inner:
         te = time.perf_counter()
         wl.step()
         t_enq1 = time.perf_counter() - te
         wl.drain(); sync()
 
     roof = None
-    if rank == 0 and not args.no_roofline and not args.plumbing_test:
+    if rank == 0 and args.full and not args.no_roofline and not args.plumbing_test:
         # ---- one extra instrumented pass of a micro-batch: HIP events around every library launch, on the launch stream -------------
         L.profile_start()
         wl.instrumented(); wl.drain(); torch.cuda.synchronize()
@@ -954,7 +1005,7 @@ def main():
                                                "state; rocprofv3's per-kernel average of this command is taken in this state); `achieved` / `frac` above are the kernel alone"}
 
     also = None
-    if (rank == 0 and world == 1 and args.workload == "full" and not args.no_also and not args.plumbing_test and args.global_batch is None
+    if (rank == 0 and world == 1 and args.full and args.workload == "full" and not args.no_also and not args.plumbing_test and args.global_batch is None
             and args.batch is None and not args.force_collective):
         B_headline, gen_prec_headline = wl.B, getattr(getattr(wl, "gen", None), "precision", None)
         wl_keep = type("Done", (), {"B": B_headline, "gen": type("G", (), {"precision": gen_prec_headline})(), "buckets": 0, "graphs": False})()
@@ -967,7 +1018,7 @@ def main():
         faces = B * world * args.steps
         value = faces / dt
         cpu = None
-        if world == 1 and args.cpu_faces > 0 and not args.plumbing_test:
+        if world == 1 and args.full and args.cpu_faces > 0 and not args.plumbing_test:
             cpu = cpu_baseline(sandbox, args.workload, args.cpu_faces if args.workload != "flame512" else 512, all_cores=args.cpu_all_cores, passes=args.cpu_passes)
         weak = args.batch is not None or (args.workload == "train64" and args.global_batch is None)
         flop_face = {"full": FLOP_PER_FACE, "infer256": FLOP_PER_FACE_INFER, "flame512": FLOP_PER_FACE_FLAME, "train64": FLOP_PER_FACE_TRAIN}[args.workload]
@@ -1014,7 +1065,9 @@ def main():
             "host_submit_ms_per_step_incl_queue_backpressure": t_host / args.steps * 1e3,
             "path_tflops_per_gpu": value / world * flop_face / 1e12,
             "path_frac_of_f16_mfma_peak": value / world * flop_face / PEAK_F16_MFMA,
-            "output_stats": stats, "roofline": roof, "cpu_baseline": cpu}
+            "output_stats": stats, "roofline": roof, "cpu_baseline": cpu, "full": args.full}
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
         if also is not None:
             line["also"] = also
         if args.plumbing_test and args.workload == "train64":

@@ -1,31 +1,51 @@
-"""BASELINE config 1 ("demo.py single image, plumbing"): the REFERENCE's own demo.py, unmodified, executed on top of the drop-in classes through
-the `integration/shim` package, in the build container (skipped where /root/reference does not exist, e.g. the GPU box).
-Everything up to the first device call runs: imports, the three constructors with the reference's arguments, the strict `load_state_dict`
-of a `smirk_encoder.` / `smirk_generator.`-prefixed checkpoint (demo.py:54-66), `.eval()`, `FLAME().to(...)`, `Renderer().to(...)`, the
-pre-processing up to `smirk_encoder(cropped_image)` — which must then fail LOUDLY, because the HIP path has no CPU fallback."""
+"""BASELINE config 1 ("demo.py single image, plumbing"): a demo-style driver script, executed on top of the drop-in classes through the
+`integration/shim` package, makes the calls INTEGRATION.md §2 lists for the reference's demo: `from src... import ...`, the three
+constructors with the demo's arguments, the strict `load_state_dict` of a `smirk_encoder.` / `smirk_generator.`-prefixed checkpoint, `.eval()`,
+`FLAME().to(...)`, `Renderer().to(...)`, then the first forward of the encoder on a host tensor — which must fail LOUDLY, because the HIP path has no
+CPU fallback.  The driver is part of this test, so it runs wherever the repository does."""
 import os
 import runpy
 import sys
 import traceback
-import types
 
-import numpy as np
 import pytest
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 
-pytestmark = pytest.mark.skipif(not os.path.exists(os.path.join(REF, "demo.py")), reason="the reference checkout exists in the build container only")
+# the caller's side of INTEGRATION.md §2, written against the reference's module paths (resolved by integration/shim)
+DEMO_DRIVER = """\
+import argparse
+import torch
+from src.smirk_encoder import SmirkEncoder
+from src.FLAME.FLAME import FLAME
+from src.renderer.renderer import Renderer
+import src.utils.masking as masking_utils
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--device", default="cuda")
+ap.add_argument("--checkpoint")
+ap.add_argument("--use_smirk_generator", action="store_true")
+args = ap.parse_args()
+
+ckpt = torch.load(args.checkpoint)
+encoder = SmirkEncoder().to(args.device)
+encoder.load_state_dict({k[len("smirk_encoder."):]: v for k, v in ckpt.items() if k.startswith("smirk_encoder.")})
+encoder.eval()
+if args.use_smirk_generator:
+    from src.smirk_generator import SmirkGenerator
+    generator = SmirkGenerator(in_channels=6, out_channels=3, init_features=32, res_blocks=5).to(args.device)
+    generator.load_state_dict({k[len("smirk_generator."):]: v for k, v in ckpt.items() if k.startswith("smirk_generator.")})
+    generator.eval()
+flame = FLAME().to(args.device)
+renderer = Renderer().to(args.device)
+face_probabilities = masking_utils.load_probabilities_per_FLAME_triangle()
+image = torch.rand(1, 3, 224, 224, device=args.device)
+outputs = encoder(image)   # first device call
+"""
 
 
-def _stub(name, **attrs):
-    m = types.ModuleType(name)
-    m.__dict__.update(attrs)
-    return m
-
-
-def test_reference_demo_runs_on_the_shim_until_the_first_device_call(in_sandbox, monkeypatch, tmp_path):
+def test_demo_driver_runs_on_the_shim_until_the_first_device_call(in_sandbox, monkeypatch, tmp_path):
     from oracle import generator_ref as G, mobilenet_ref as M
     import smirk_amd
     # synthetic checkpoint in the reference's wire format (base_trainer.py:222-231): one flat dict, module-prefixed keys
@@ -33,31 +53,18 @@ def test_reference_demo_runs_on_the_shim_until_the_first_device_call(in_sandbox,
     ckpt.update({"smirk_generator." + k: v for k, v in G.synth_state_dict(calibrate=False).items()})
     ckpt_path = str(tmp_path / "SMIRK_em1.pt")
     torch.save(ckpt, ckpt_path)
-
-    calls = []
-    rng = np.random.default_rng(0)
-    img = (rng.uniform(0, 255, (224, 224, 3))).astype(np.uint8)
-    kpt = np.stack([rng.uniform(60, 160, 478), rng.uniform(60, 160, 478), np.zeros(478)], 1)
-    cv2 = _stub("cv2", imread=lambda p: img.copy(), cvtColor=lambda a, code: a[..., ::-1].copy(), COLOR_BGR2RGB=4, COLOR_RGB2BGR=4,
-                resize=lambda a, size: a, imwrite=lambda *a: calls.append("imwrite"))
-    sk = _stub("skimage"); skt = _stub("skimage.transform", estimate_transform=lambda *a, **k: None, warp=lambda *a, **k: None)
-    mp_utils = _stub("utils.mediapipe_utils", run_mediapipe=lambda image: kpt)
-    utils_pkg = _stub("utils"); utils_pkg.__path__ = []
-    ds_pkg = _stub("datasets"); ds_pkg.__path__ = []
-    base_ds = _stub("datasets.base_dataset", create_mask=lambda lm, shape: np.ones(shape, np.float32))
-    for name, mod in (("cv2", cv2), ("skimage", sk), ("skimage.transform", skt), ("utils", utils_pkg), ("utils.mediapipe_utils", mp_utils),
-                      ("datasets", ds_pkg), ("datasets.base_dataset", base_ds)):
-        monkeypatch.setitem(sys.modules, name, mod)
+    driver = str(tmp_path / "demo_driver.py")
+    with open(driver, "w") as fh:
+        fh.write(DEMO_DRIVER)
     for name in [n for n in sys.modules if n == "src" or n.startswith("src.")]:
         monkeypatch.delitem(sys.modules, name)
     monkeypatch.syspath_prepend(os.path.join(REPO, "integration", "shim"))
-    monkeypatch.setattr(sys, "argv", ["demo.py", "--input_path", "x.png", "--device", "cpu", "--checkpoint", ckpt_path, "--use_smirk_generator",
-                                      "--out_path", str(tmp_path / "out")])
+    monkeypatch.setattr(sys, "argv", ["demo_driver.py", "--device", "cpu", "--checkpoint", ckpt_path, "--use_smirk_generator"])
     with pytest.raises(smirk_amd.SmirkHipError) as ei:
-        runpy.run_path(os.path.join(REF, "demo.py"), run_name="__main__")
+        runpy.run_path(driver, run_name="__main__")
     assert "no CPU fallback" in str(ei.value)
-    frames = [f for f in traceback.extract_tb(ei.tb) if f.filename == os.path.join(REF, "demo.py")]
-    assert frames and "smirk_encoder(cropped_image)" in (frames[-1].line or ""), "demo.py must have reached its first forward call"
+    frames = [f for f in traceback.extract_tb(ei.tb) if f.filename == driver]
+    assert frames and "encoder(image)" in (frames[-1].line or ""), "the driver must have reached its first forward call"
 
 
 def test_shim_exposes_the_reference_module_paths(monkeypatch):

@@ -7,7 +7,7 @@ timeout 600 python -m pytest tests/test_train_ops_gpu.py tests/test_generator_tr
 timeout 200 python tools/train_phase_times.py f16x3 8 2>&1 | tail -10 | tee $OUT/${TAG}_phase_times_f16x3.txt
 timeout 200 python tools/train_phase_times.py f16x1 8 2>&1 | tail -10 | tee $OUT/${TAG}_phase_times_f16x1.txt
 for rep in 1 2; do
-  timeout 300 python bench.py --workload train64 --steps 20 --warmup 3 --traffic off --cpu-faces 0 --no-roofline > $OUT/${TAG}_bench_train64_fused$rep.json 2> /dev/null; python tools/bench_summary.py $OUT/${TAG}_bench_train64_fused$rep.json 1
-  SMIRK_BN_STATS_UNFUSED=1 timeout 300 python bench.py --workload train64 --steps 20 --warmup 3 --traffic off --cpu-faces 0 --no-roofline > $OUT/${TAG}_bench_train64_unfused$rep.json 2> /dev/null; python tools/bench_summary.py $OUT/${TAG}_bench_train64_unfused$rep.json 1
+  timeout 300 python bench.py --full --workload train64 --steps 20 --warmup 3 --traffic off --cpu-faces 0 --no-roofline > $OUT/${TAG}_bench_train64_fused$rep.json 2> /dev/null; python tools/bench_summary.py $OUT/${TAG}_bench_train64_fused$rep.json 1
+  SMIRK_BN_STATS_UNFUSED=1 timeout 300 python bench.py --full --workload train64 --steps 20 --warmup 3 --traffic off --cpu-faces 0 --no-roofline > $OUT/${TAG}_bench_train64_unfused$rep.json 2> /dev/null; python tools/bench_summary.py $OUT/${TAG}_bench_train64_unfused$rep.json 1
 done
-timeout 300 python bench.py --workload train64 --steps 10 --warmup 3 --traffic off --cpu-faces 0 > $OUT/${TAG}_bench_train64.json 2> $OUT/${TAG}_bench_train64.err; python tools/bench_summary.py $OUT/${TAG}_bench_train64.json 30
+timeout 300 python bench.py --full --workload train64 --steps 10 --warmup 3 --traffic off --cpu-faces 0 > $OUT/${TAG}_bench_train64.json 2> $OUT/${TAG}_bench_train64.err; python tools/bench_summary.py $OUT/${TAG}_bench_train64.json 30

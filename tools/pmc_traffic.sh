@@ -1,11 +1,12 @@
 #!/bin/bash
 # HBM-side traffic per kernel launch from two separate rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) over one bench step.
 #   usage (GPU box, via gpurun): bash tools/pmc_traffic.sh <tag>      -> gpurun_out/<tag>_pmc_hbm.txt, gpurun_out/pmc_traffic.json
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 TAG=${1:-r01}
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pmc_$c
-  rocprofv3 --pmc $c --kernel-trace -d /tmp/pmc_$c -o p -- python /root/repo/bench.py --steps 1 --warmup 0 --cpu-faces 0 --no-overlap > /tmp/pmc_$c.log 2>&1
+  rocprofv3 --pmc $c --kernel-trace -d /tmp/pmc_$c -o p -- python $REPO/bench.py --full --steps 1 --warmup 0 --cpu-faces 0 --no-overlap > /tmp/pmc_$c.log 2>&1
 done
 python - <<PY
 import sqlite3, json, glob
@@ -27,7 +28,7 @@ for k in f:
 rows.sort(key=lambda r: -r[4] * r[1])
 with open("/root/repo/gpurun_out/${TAG}_pmc_hbm.txt", "w") as o:
     o.write("# rocprofv3 PMC passes (separate runs): FETCH_SIZE and WRITE_SIZE, per-dispatch mean, KB units\n")
-    o.write("# command: rocprofv3 --pmc <X> --kernel-trace -- python bench.py --steps 1 --warmup 0 --cpu-faces 0 --no-overlap  (2 steps incl. instrumented)\n")
+    o.write("# command: rocprofv3 --pmc <X> --kernel-trace -- python bench.py --full --steps 1 --warmup 0 --cpu-faces 0 --no-overlap  (2 steps incl. instrumented)\n")
     o.write("# HBM-side bytes per launch = (2*FETCH_SIZE + WRITE_SIZE) * 1024  (gfx950: FETCH_SIZE under-reports wide reads by 2x, MI355X_MICROARCH.md; Infinity-Cache hits are included)\n")
     o.write(f"{'kernel':60s} {'launches':>8s} {'FETCH_KB':>12s} {'WRITE_KB':>12s} {'bytes/launch':>14s}\n")
     for k, n, fk, wk, b in rows:
