@@ -1,4 +1,12 @@
 // Error strings / ABI version of libsmirk_hip.so.
+#include <stdlib.h>
+#include <string.h>
+
+#include <map>
+#include <mutex>
+#include <utility>
+#include <vector>
+
 #include "common.h"
 
 extern "C" const char* smirk_strerror(int code) {
@@ -14,11 +22,57 @@ extern "C" const char* smirk_strerror(int code) {
 
 extern "C" int smirk_abi_version(void) { return 11; }
 
+// ---- environment switches (switches.h: names, values, defaults) -------------------------------------------------------------------------
+int smirk_switch(SmirkSwitch s) {
+    static const char* const names[] = {"SMIRK_IGEMM_HALO", "SMIRK_IGEMM_PP", "SMIRK_CONV_RING", "SMIRK_DISABLE_PATCH_KERNEL", "SMIRK_DISABLE_ENC1_FUSED",
+                                        "SMIRK_DISABLE_MBCONV_IMAGE", "SMIRK_DISABLE_MBCONV_TILE", "SMIRK_DISABLE_MBCONV_FUSED",
+                                        "SMIRK_DISABLE_ENCODER_HEAD_FUSED", "SMIRK_GEN_SPLIT_CHAINS", "SMIRK_WGRAD_F16"};
+    static_assert(sizeof(names) / sizeof(names[0]) == SMIRK_SW_COUNT, "one name per SmirkSwitch");
+    const char* e = getenv(names[s]);
+    switch (s) {
+        case SMIRK_SW_IGEMM_HALO:
+        case SMIRK_SW_CONV_RING: return !e || e[0] != '0';
+        case SMIRK_SW_IGEMM_PP: return !e ? 1 : e[0] == '0' ? 0 : e[0] == 'a' ? 2 : 1;
+        case SMIRK_SW_GEN_SPLIT_CHAINS: return !e ? 0 : e[0] == '0' ? 1 : e[0] == '3' ? 3 : 2;
+        case SMIRK_SW_WGRAD_F16: return e ? atoi(e) : SMIRK_WGRAD_F16_DEFAULT;
+        default: return e != nullptr;                                            // SMIRK_DISABLE_*: set means off, whatever the value
+    }
+}
+
+// ---- per-device launch setup (common.h) ---------------------------------------------------------------------------------------------------
+namespace {
+std::mutex g_dev_mu;
+std::map<std::pair<int, const void*>, size_t> g_lds_raised;                     // (device, kernel) -> largest dynamic-LDS limit raised so far
+std::map<int, int> g_dev_cus;
+}  // namespace
+
+int smirk_raise_dynamic_lds(const void* kernel, size_t bytes) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return SMIRK_ERR_LAUNCH; }
+    std::lock_guard<std::mutex> lk(g_dev_mu);
+    size_t& raised = g_lds_raised[{dev, kernel}];
+    if (bytes <= raised) return SMIRK_OK;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) { (void)hipGetLastError(); return SMIRK_ERR_LAUNCH; }
+    raised = bytes;
+    return SMIRK_OK;
+}
+
+int smirk_device_cus() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 256; }
+    std::lock_guard<std::mutex> lk(g_dev_mu);
+    auto it = g_dev_cus.find(dev);
+    if (it != g_dev_cus.end()) return it->second;
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) { (void)hipGetLastError(); cus = 256; }
+    g_dev_cus[dev] = cus;
+    return cus;
+}
+
 // ---- split-fp16 range flag (common.h: smirk_range_audit8) -------------------------------------------------------------------------------
 // ONE host-pinned, device-mapped word per process.  Kernels store a 1 into it (system-scope store, cold path) when a value they are about to split into the
 // storage format would overflow the fp16 `hi` half; the host READS it with a plain load — no stream or device synchronisation — when the next forward of a
 // module starts (or when the user asks, smirk_range_flag_peek after a synchronisation of their own).  Sticky until smirk_range_flag_clear().
-#include <mutex>
 namespace {
 std::once_flag g_range_once;
 unsigned* g_range_host = nullptr;
@@ -40,10 +94,6 @@ extern "C" unsigned smirk_range_flag_peek(void) { return g_range_host ? *(volati
 extern "C" void smirk_range_flag_clear(void) { if (g_range_host) *(volatile unsigned*)g_range_host = 0u; }
 
 // ---- launch profiler ---------------------------------------------------------------------------------------------------------------
-#include <mutex>
-#include <string.h>
-#include <vector>
-
 bool g_smirk_prof_on = false;
 namespace {
 struct ProfRec { char name[120]; double flop, bytes; hipEvent_t e0, e1; };

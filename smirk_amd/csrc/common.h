@@ -6,6 +6,7 @@
 #include <atomic>
 
 #include "../../include/smirk_hip.h"
+#include "switches.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -89,15 +90,28 @@ __device__ __forceinline__ void smirk_range_audit1(float v) {                  /
     if (__builtin_expect(!(fabsf(v) < SMIRK_F16_RANGE_LIMIT), 0)) smirk_range_trip();
 }
 unsigned* smirk_range_flag_device_ptr();                                        // capi.hip: device address of the host-pinned word (nullptr if it cannot be mapped)
-static inline void smirk_range_bind_tu() {
+// The binding is a synchronous copy: it is not issued while the launch stream is being captured (the unit stays unbound and binds at its next launch outside a
+// capture), and a unit counts as bound only once the copy succeeded, or failed because the unit has no audited kernels (no such symbol), or no flag word exists.
+static inline void smirk_range_bind_tu(hipStream_t st) {
     static std::atomic<unsigned long long> bound{0};                            // one bit per device, per translation unit
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return; }
     if ((bound.load(std::memory_order_relaxed) >> dev) & 1ull) return;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return; }
     unsigned* p = smirk_range_flag_device_ptr();
-    if (p && hipMemcpyToSymbol(HIP_SYMBOL(smirk_range_flag_dev), &p, sizeof(p)) != hipSuccess) (void)hipGetLastError();   // (a unit without audited kernels has no such symbol)
+    if (p) {
+        const hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(smirk_range_flag_dev), &p, sizeof(p));
+        if (e != hipSuccess) (void)hipGetLastError();
+        if (e != hipSuccess && e != hipErrorInvalidSymbol) return;
+    }
     bound.fetch_or(1ull << dev, std::memory_order_relaxed);
 }
+
+// Per-device launch setup (capi.hip).  smirk_raise_dynamic_lds: raises `kernel`'s dynamic-LDS limit on the current device to `bytes` unless an earlier call
+// already raised it at least that far (thread-safe; SMIRK_OK or SMIRK_ERR_LAUNCH).  smirk_device_cus: CU count of the current device (256 if it cannot be read).
+int smirk_raise_dynamic_lds(const void* kernel, size_t bytes);
+int smirk_device_cus();
 
 static inline size_t smirk_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
@@ -146,7 +160,7 @@ struct SmirkLaunchScope {
 };
 #define SMIRK_LAUNCH(kernel, grid, block, lds, st, ...)                                   \
     do {                                                                                  \
-        smirk_range_bind_tu();                                                            \
+        smirk_range_bind_tu((hipStream_t)(st));                                           \
         SmirkLaunchScope smirk_launch_scope_(#kernel, (hipStream_t)(st));                 \
         hipLaunchKernelGGL(kernel, grid, block, lds, st, __VA_ARGS__);                    \
     } while (0)

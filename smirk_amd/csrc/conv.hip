@@ -725,13 +725,12 @@ static int conv_dispatch_one(const SmirkConvDesc* d, const void* in0, const void
     const long long M = (long long)d->B * d->Ho * d->Wo;
     if (M > (1ll << 30) || (long long)d->B * d->H * d->W > (1ll << 30)) return SMIRK_ERR_UNSUPPORTED;
     a.M = (int)M;
-    a.ablate = 0;
     a.stats = nullptr;
     a.psh = 0;
     if (d->KH == 3)                                             // only convs with a halo profit from patch ordering
         while (a.psh < 4 && d->Ho % (2 << a.psh) == 0 && d->Wo % (2 << a.psh) == 0) ++a.psh;
     hipStream_t st = (hipStream_t)stream;
-    static const bool no_patch = getenv("SMIRK_DISABLE_PATCH_KERNEL") != nullptr;   // A/B switch for tools/ and tests: neither the patch nor the ring kernels
+    const bool no_patch = smirk_switch(SMIRK_SW_DISABLE_PATCH_KERNEL);         // A/B switch: neither the patch nor the ring kernels
     // F16X1 lives in conv_igemm_kernel only: the specialised kernels below issue the three-MFMA product unconditionally
     if (split && !x1 && !no_patch && smirk_conv3x3_ring64_eligible(d, residual != nullptr))         // conv_ring.hip: the 64-output-channel layers on large images
         return smirk_conv3x3_ring64_launch(d, in0, in1, w, scale, shift, out, nullptr, st, stats, stats_rows);      // (they write statistics only for a raw epilogue)

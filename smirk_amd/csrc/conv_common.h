@@ -12,7 +12,6 @@ struct ConvArgs {
     const float *in0, *in1, *w, *scale, *shift, *residual;   // F16X3: in0/in1/w/residual/out are split-fp16 tensors viewed as dwords
     float* out;
     int M, N, K, Cin;
-    int ablate;    // reserved for ablation experiments (unused in the shipped kernels)
     float* stats;  // train mode (BatchNorm statistics from the accumulators): per-tile partial column sums [rows][N][2] = (sum z, sum z^2) in fp32, or nullptr.
                    // Every kernel family that honours it states its row count through smirk_conv_stats_rows(); the fixed-order fp64 reduction over the rows is
                    // bn_finalize_partials_kernel (train.hip)

@@ -19,7 +19,6 @@
 //
 // Bound: MFMA (dense fp16 2.5 PF, 3 MFMAs per product).  Algorithmic flop = 2*M*N*K per launch.
 #include <stdio.h>
-#include <stdlib.h>
 #include <type_traits>
 
 #include "conv_common.h"
@@ -32,21 +31,6 @@
 #define HS_DEFAULT_EB 0
 
 typedef __attribute__((address_space(3))) void* hs_lptr_t;
-
-// Phase timeline (tools/halo_timeline.py), compiled only into -DSMIRK_DEBUG_HOOKS variant builds (tools/build_variant.sh): waves 0 and 4 of a few
-// workgroups stamp s_memtime at the four phase boundaries of every chunk into spare LDS and dump it at the end of the kernel.
-#ifdef SMIRK_DEBUG_HOOKS
-__device__ long long* g_hs_dbg = nullptr;                            // [8 workgroups][2 waves][HS_DBG_N] stamps
-#define HS_DBG_N 1024
-#define HS_DBG_LDS (2 * HS_DBG_N * 8)
-#define HS_STAMP()                                                                                             \
-    do {                                                                                                       \
-        if (dbg_on && dbg_i < HS_DBG_N) { dbg_lds[dbg_i] = (long long)__builtin_readcyclecounter(); ++dbg_i; } \
-    } while (0)
-#else
-#define HS_DBG_LDS 0
-#define HS_STAMP() do {} while (0)
-#endif
 
 template <int K>
 using hs_ic = std::integral_constant<int, K>;
@@ -82,13 +66,6 @@ __device__ __forceinline__ void conv_halo_body(const ConvArgs& a) {
     const int W = d.W, HW = d.H * d.W;
     const int fr = lane & 31, hb = lane >> 5;
 
-#ifdef SMIRK_DEBUG_HOOKS
-    const int dbg_slot = (blockIdx.x % 97 == 0) ? (int)(blockIdx.x / 97) : -1;
-    const bool dbg_on = g_hs_dbg != nullptr && dbg_slot >= 0 && dbg_slot < 8 && (tid == 0 || tid == 256);
-    long long* dbg_lds = (long long*)(lds + A0 + 2 * ASTRIDE) + (tid >> 8) * HS_DBG_N;
-    int dbg_i = 0;
-    const long long dbg_t_entry = (long long)__builtin_readcyclecounter();
-#endif
     // ---- zero rows (read by every tap that falls into the zero padding) ------------------------------------------------------------------------
     if (tid < 64) *(float*)(lds + A0 + (tid >> 5) * ASTRIDE + ABUF + (tid & 31) * 4) = 0.f;
 
@@ -154,7 +131,6 @@ __device__ __forceinline__ void conv_halo_body(const ConvArgs& a) {
     auto body = [&](int cc, int acur, int anext, auto tapc) {
         constexpr int TAP = decltype(tapc)::value, ST = TAP % 3;
         // ---- load phase ------------------------------------------------------------------------------------------------------------------------
-        HS_STAMP();
         {
             const unsigned t = tabA[TAP];
             const unsigned a0 = (t & 0xffffu) + (unsigned)acur, a1 = (t >> 16) + (unsigned)acur;
@@ -196,11 +172,9 @@ __device__ __forceinline__ void conv_halo_body(const ConvArgs& a) {
         else if constexpr (NLD == 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
         else if constexpr (NLD == 1) asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        HS_STAMP();
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        HS_STAMP();
         // ---- matrix phase: 24 MFMAs, operands in registers; dependent accumulations four instructions apart; the DMA instructions left over from
         //      the load phase go out one after every fourth MFMA (an LDS-DMA costs ~60 issue cycles among bare MFMAs, MI355X_MICROARCH.md) ---------
         __builtin_amdgcn_s_setprio(1);
@@ -227,7 +201,6 @@ __device__ __forceinline__ void conv_halo_body(const ConvArgs& a) {
                 }
         };
         auto hand_over = [&]() {                                     // the barrier that ends the matrix phase
-            HS_STAMP();
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
@@ -318,14 +291,7 @@ __device__ __forceinline__ void conv_halo_body(const ConvArgs& a) {
     if (group == 0) __builtin_amdgcn_s_barrier();                   // both groups have executed the same number of barriers ...
     __builtin_amdgcn_s_barrier();                                   // ... and every wave's DMA has retired
 
-#ifdef SMIRK_DEBUG_HOOKS
-    HS_STAMP();
-    if (dbg_on)
-        for (int k = 0; k < dbg_i; ++k) g_hs_dbg[(dbg_slot * 2 + (tid >> 8)) * HS_DBG_N + k] = dbg_lds[k];
-    __builtin_amdgcn_s_barrier();
-#endif
     // ---- epilogue: per-wave transpose through LDS, whole 8-channel groups, BN scale/shift + residual + ReLU, re-split ---------------------------
-    HS_STAMP();
     SmirkRangeAcc rng;                                              // split-fp16 range audit (common.h): one running max per lane, tested once after the stores
     float st1[2] = {0.f, 0.f}, st2[2] = {0.f, 0.f};                 // STATS (train mode): this lane's column sums over the wave's 64 rows (conv_common.h stats_block)
 #pragma unroll
@@ -384,14 +350,6 @@ __device__ __forceinline__ void conv_halo_body(const ConvArgs& a) {
             if ((lane >> 5) == 0) { prow[n * 2] = t1; prow[n * 2 + 1] = t2; }
         }
     }
-#ifdef SMIRK_DEBUG_HOOKS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    HS_STAMP();
-    if (dbg_on) {
-        long long* g = g_hs_dbg + (dbg_slot * 2 + (tid >> 8)) * HS_DBG_N;
-        g[HS_DBG_N - 3] = dbg_lds[dbg_i - 2]; g[HS_DBG_N - 2] = dbg_lds[dbg_i - 1]; g[HS_DBG_N - 4] = dbg_t_entry;
-    }
-#endif
 }
 
 template <int NPA, int EB>
@@ -404,16 +362,10 @@ __global__ __launch_bounds__(512, 2) void conv_halo_stats_kernel(ConvArgs a) { c
 template <int NPA>
 __global__ __launch_bounds__(512, 2) void conv_halo_x1_stats_kernel(ConvArgs a) { conv_halo_body<NPA, 0, true, true>(a); }
 
-static int hs_env_mode() {                                           // $SMIRK_IGEMM_HALO: "0" off; unset / anything else = every eligible geometry
-    const char* env = getenv("SMIRK_IGEMM_HALO");                   // read per call: tests toggle it
-    return !env ? 1 : env[0] == '0' ? 0 : env[0] == 'a' ? 2 : 1;
-}
-
 // Serves: split-fp16, 3x3, stride 1, pad 1, NHWC out, both sources power-of-two multiples of 32 channels, N a multiple of 128, W <= 63, operands < 2 GiB.
 bool smirk_conv_halo_eligible(const ConvArgs& a) {
     const SmirkConvDesc& d = a.d;
-    const int mode = hs_env_mode();
-    if (mode == 0) return false;
+    if (!smirk_switch(SMIRK_SW_IGEMM_HALO)) return false;
     if (d.KH != 3 || d.KW != 3 || d.stride != 1 || d.out_mode != SMIRK_OUT_NHWC || d.pad_t != 1 || d.pad_l != 1) return false;
     if (d.Ho != d.H || d.Wo != d.W || d.W > 63 || d.W < 2 || d.H < 2) return false;
     if (d.C0 % CV_BK || d.C1 % CV_BK || (d.C0 & (d.C0 - 1)) || (d.C1 & (d.C1 - 1))) return false;
@@ -431,16 +383,10 @@ bool smirk_conv_halo_eligible(const ConvArgs& a) {
 }
 
 template <int NPA, int EB, bool X1>
-static int hs_launch(const ConvArgs& a, hipStream_t st, size_t lds, int dev) {
-    static bool attr_done[64] = {};                                  // hipFuncSetAttribute is per-device state (one process may drive several GPUs)
+static int hs_launch(const ConvArgs& a, hipStream_t st, size_t lds) {
     const void* fn = X1 ? (const void*)conv_halo_x1_kernel<NPA> : (const void*)conv_halo_kernel<NPA, EB>;
     const void* fns = X1 ? (const void*)conv_halo_x1_stats_kernel<NPA> : (const void*)conv_halo_stats_kernel<NPA, EB>;
-    if (!attr_done[dev]) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(fns, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return SMIRK_ERR_LAUNCH;
-        attr_done[dev] = true;
-    }
+    if (const int rc = smirk_raise_dynamic_lds(a.stats ? fns : fn, 160 * 1024)) return rc;
     const int ntm = (a.M + HS_BM - 1) / HS_BM, ntn = a.N / HS_BN;
     if (g_smirk_prof_on) {
         const double px = (double)a.d.B * a.d.H * a.d.W;
@@ -462,19 +408,9 @@ static int hs_launch(const ConvArgs& a, hipStream_t st, size_t lds, int dev) {
 
 int smirk_conv_halo_launch(const ConvArgs& a, hipStream_t st, bool x1) {
     const int npa = (HS_BM + 2 * (a.d.W + 1) + 63) / 64;             // 64 halo rows per piece index (8 waves x 8 rows)
-    const size_t lds = HS_BRING_BYTES + 2 * ((size_t)(npa <= 5 ? 5 : 6) * 8 * 1024 + 128) + HS_DBG_LDS;
-#ifdef SMIRK_DEBUG_HOOKS
-    {
-        const char* e = getenv("SMIRK_HALO_DBG");                   // hex device address of a zeroed int64 buffer [8][2][HS_DBG_N], tools/halo_timeline.py
-        long long* p = e ? (long long*)strtoull(e, nullptr, 16) : nullptr;
-        if (hipMemcpyToSymbolAsync(HIP_SYMBOL(g_hs_dbg), &p, sizeof(p), 0, hipMemcpyHostToDevice, st) != hipSuccess) return SMIRK_ERR_LAUNCH;
-    }
-#endif
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64) return SMIRK_ERR_UNSUPPORTED;
+    const size_t lds = HS_BRING_BYTES + 2 * ((size_t)(npa <= 5 ? 5 : 6) * 8 * 1024 + 128);
     // (EB = MFMAs issued after the hand-over barrier: 4 / 8 measured 3-7 % slower without the time stamps in, profiles/r03b_halo_nl_sweep.txt, r04x_kernel_selection.txt;
     // the $SMIRK_HALO_EB switch and its instantiations left the library in round 5)
-    if (x1) return npa <= 5 ? hs_launch<5, HS_DEFAULT_EB, true>(a, st, lds, dev) : hs_launch<6, HS_DEFAULT_EB, true>(a, st, lds, dev);
-    return npa <= 5 ? hs_launch<5, HS_DEFAULT_EB, false>(a, st, lds, dev) : hs_launch<6, HS_DEFAULT_EB, false>(a, st, lds, dev);
+    if (x1) return npa <= 5 ? hs_launch<5, HS_DEFAULT_EB, true>(a, st, lds) : hs_launch<6, HS_DEFAULT_EB, true>(a, st, lds);
+    return npa <= 5 ? hs_launch<5, HS_DEFAULT_EB, false>(a, st, lds) : hs_launch<6, HS_DEFAULT_EB, false>(a, st, lds);
 }

@@ -13,7 +13,6 @@
 //
 // Bound: HBM (activation read 1.27x + write 1x) once the DMA is hidden; MFMA work is ~40 % of that time.
 #include <type_traits>
-#include <stdlib.h>
 
 #include "common.h"
 
@@ -73,7 +72,6 @@ struct PatchArgs {
     const float *fw, *fb;
     float* fout;
     int fcout;
-    long long* dbg;  // optional phase time stamps (s_memtime) of wave 0 of a few workgroups: [block][item][5]; tools/patch_timeline.py
     int use_buf;     // operand DMA through buffer resources (32-bit per-lane offsets, OOB rows for the zero padding): C0, C1 powers of two, tensors < 2 GiB
 };
 
@@ -273,7 +271,7 @@ __global__ __launch_bounds__(256 * GROUPS, (NST == 1 && GROUPS == 1) ? 2 : 1) vo
     int nq_w = 0;
 #pragma unroll
     for (int q = 0; q < NQ; ++q) nq_w += ((q * 4 + swave) * 8 < PPIXT) ? 1 : 0;
-    int st = 0, dbg_n = 0;
+    int st = 0;
     bool first = true;
     SmirkRangeAcc rng;
     if (GROUPS == 2 && !(item < nitem)) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); }   // idle group: still owes its weight share + the barrier
@@ -281,9 +279,6 @@ __global__ __launch_bounds__(256 * GROUPS, (NST == 1 && GROUPS == 1) ? 2 : 1) vo
         int b, oy0, ox0, cc;
         item_patch(item, b, oy0, ox0, cc);
         const int nxt = next_item(item);
-        const bool stamp = a.dbg && wave_all == 0 && lane == 0 && (blockIdx.x & 63) == 0 && dbg_n < 48;
-        long long* dbgp = stamp ? a.dbg + ((size_t)(blockIdx.x >> 6) * 48 + dbg_n) * 6 : nullptr;
-        if (stamp) { dbgp[0] = __builtin_amdgcn_s_memtime(); ++dbg_n; }
         if (NST == 3 && nxt < nitem) {                            // item + 1 may stay in flight
             if (nq_w == NQ) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NQ) : "memory");
             else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NQ - 1) : "memory");
@@ -293,7 +288,6 @@ __global__ __launch_bounds__(256 * GROUPS, (NST == 1 && GROUPS == 1) ? 2 : 1) vo
         if (GROUPS == 2 && first) { __syncthreads(); first = false; }   // the OTHER group's share of the weight DMA has landed too
         else gbar();
         // stage st (and, first time, the weights) has landed
-        if (stamp) dbgp[1] = __builtin_amdgcn_s_memtime();
         if (NST == 2 && nxt < nitem) issue_item(nxt, st ^ 1);    // the other stage is free: refill it under the MFMAs
         if (NST == 3 && nxt < nitem) {
             const int nn = next_item(nxt);
@@ -350,7 +344,6 @@ __global__ __launch_bounds__(256 * GROUPS, (NST == 1 && GROUPS == 1) ? 2 : 1) vo
                 __builtin_amdgcn_sched_barrier(0);               // the next step's reads stay behind this step's MFMAs in program order
             }
         }
-        if (stamp) dbgp[2] = __builtin_amdgcn_s_memtime();
         if (cc == a.nchunk - 1) {
             // ---- epilogue: this stage's LDS is dead now (next DMA went to the other stage): use it as per-wave transpose buffers
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -421,13 +414,10 @@ __global__ __launch_bounds__(256 * GROUPS, (NST == 1 && GROUPS == 1) ? 2 : 1) vo
                 wave_lds_fence();          // per-wave transpose buffer: LDS ops of one wave execute in order
             }
         }
-        if (stamp) dbgp[3] = __builtin_amdgcn_s_memtime();
         if (NST == 1) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             gbar();                                               // everyone is done with the only stage (compute or epilogue)
-            if (stamp) dbgp[4] = __builtin_amdgcn_s_memtime();
             if (nxt < nitem) issue_item(nxt, 0);
-            if (stamp) dbgp[5] = __builtin_amdgcn_s_memtime();
         } else if (NST == 2) {
             st ^= 1;
         } else {
@@ -679,14 +669,6 @@ int smirk_conv3x3_patch_launch(const SmirkConvDesc* d, const void* in0, const vo
                                int fcout) {
     PatchArgs a;
     a.fw = fw; a.fb = fb; a.fout = fout; a.fcout = fcout;
-    {   // debugging aid: SMIRK_PATCH_DBG=<device address (hex) of a zeroed int64 buffer of >= 8*48*6 entries>, see tools/patch_timeline.py
-#ifdef SMIRK_DEBUG_HOOKS                                                 /* a raw device address from the environment: variant builds only */
-        const char* e = getenv("SMIRK_PATCH_DBG");
-        a.dbg = e ? (long long*)strtoull(e, nullptr, 16) : nullptr;
-#else
-        a.dbg = nullptr;
-#endif
-    }
     a.in0 = (const float*)in0; a.in1 = (const float*)in1; a.w = (const float*)w; a.scale = scale; a.shift = shift; a.out = (float*)out;
     a.B = d->B; a.H = d->H; a.W = d->W; a.C0 = d->C0; a.C1 = d->C1; a.Cout = d->Cout; a.act = d->act;
     a.nchunk = (d->C0 + 31) / 32 + (d->C1 + 31) / 32;
@@ -703,26 +685,12 @@ int smirk_conv3x3_patch_launch(const SmirkConvDesc* d, const void* in0, const vo
                         px * (d->C0 + d->C1) * 4.0 + outb + K * d->Cout * 4.0);
     }
     if (!patch_resident(d)) {
-        static bool attr2_dev[64] = {};                              // per device ordinal (hipFuncSetAttribute is per-device state)
-        int dev2 = 0;
-        (void)hipGetDevice(&dev2);
-        bool& attr2 = attr2_dev[(dev2 >= 0 && dev2 < 64) ? dev2 : 0];
-        if (!attr2) { (void)hipFuncSetAttribute((const void*)conv3x3_patch_stream_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr2 = true; }
+        if (const int rc = smirk_raise_dynamic_lds((const void*)conv3x3_patch_stream_kernel, 160 * 1024)) return rc;
         const size_t lds2 = (size_t)(2 * WSTAGE + 2 * PSTAGE) * 4;
         SMIRK_LAUNCH(conv3x3_patch_stream_kernel, dim3(a.npatch < 256 ? a.npatch : 256), dim3(256), lds2, st, a);
         return smirk_launch_status();
     }
     const size_t wbytes = (size_t)a.nchunk * 9 * d->Cout * 32 * 4;
-    static bool attr_done_dev[64] = {};                              // per device ordinal (hipFuncSetAttribute is per-device state)
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    bool& attr_done = attr_done_dev[(dev >= 0 && dev < 64) ? dev : 0];
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void*)conv3x3_patch_kernel<1, 1, 16, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv3x3_patch_kernel<1, 2, 16, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv3x3_patch_kernel<2, 2, 16, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_done = true;
-    }
     // (round 4: two 4-wave groups sharing the weights on 16 x 16 patches, <1,1,16,2> with the LDS-counter group barrier: dec1a 7.38 -> 10.72 ms — removed again)
     // (rounds 2-4 kept three-stage-ring and two-group variants of this kernel behind $SMIRK_PATCH_RING: all measured 15-50 % slower than two single-stage workgroups
     // per CU — a lone 4-wave workgroup with one M tile per wave has two accumulator chains per wave and nothing else on its SIMD, so MFMA latency, not DMA latency,
@@ -734,6 +702,10 @@ int smirk_conv3x3_patch_launch(const SmirkConvDesc* d, const void* in0, const vo
     const int grid = a.npatch < cap ? a.npatch : cap;
     // (no statistics epilogue here: the <1,1,16,1> instantiation sits at 253 of its 256 VGPRs and the two running column sums would spill — round 6 tried; the three
     // 32-channel 224 x 224 layers it serves in train mode keep the stand-alone statistics pass, which streams them at HBM rate)
+    const void* fn = d->Cout == 32 && one_stage ? (const void*)conv3x3_patch_kernel<1, 1, 16, 1>
+                     : d->Cout == 32            ? (const void*)conv3x3_patch_kernel<1, 2, 16, 1>
+                                                : (const void*)conv3x3_patch_kernel<2, 2, 16, 1>;
+    if (const int rc = smirk_raise_dynamic_lds(fn, 160 * 1024)) return rc;
     if (d->Cout == 32 && one_stage) SMIRK_LAUNCH((conv3x3_patch_kernel<1, 1, 16, 1>), dim3(grid), dim3(256), lds, st, a);
     else if (d->Cout == 32) SMIRK_LAUNCH((conv3x3_patch_kernel<1, 2, 16, 1>), dim3(grid), dim3(256), lds, st, a);
     else SMIRK_LAUNCH((conv3x3_patch_kernel<2, 2, 16, 1>), dim3(grid), dim3(256), lds, st, a);

@@ -23,7 +23,6 @@
 //
 // Bound: MFMA (dense fp16 2.5 PF, 3 MFMAs per product).  Algorithmic flop = 2*M*N*K per launch.
 #include <stdio.h>
-#include <stdlib.h>
 #include <type_traits>
 
 #include "conv_common.h"
@@ -121,17 +120,11 @@ __global__ __launch_bounds__(512, 2) void conv_pp_kernel(ConvArgs a) {
             if constexpr (KX == 2) px += 1 - (int)((f >> 3) & 1u) * 2;
             const unsigned inval = (((f >> (4 + KY)) & (f >> (7 + KX))) & 1u) ^ 1u;    // 1: this tap of this row lies in the zero padding
             vo[p] = (((unsigned)px << sh) + col16) | (inval << 31);                    // bit 31 set => beyond num_records => the DMA writes zeros
-#ifdef SMIRK_DEBUG_HOOKS
-            if (a.ablate == 1) vo[p] = (unsigned)(tid & 63) * 16u;                    // timing experiment only: every A piece re-reads one L1-resident KiB
-#endif
         }
     };
     auto piece = [&](auto kc, auto stc) {
         constexpr int KP = decltype(kc)::value, ST = decltype(stc)::value;
         if constexpr (KP < 4) {
-#ifdef SMIRK_DEBUG_HOOKS
-            if (a.ablate == 2) return;                                               // timing experiment only: no A traffic at all
-#endif
             float* dst = smem + (((swave + 8 * KP) * PP_NSTAGE + ST) << 8);          // block swave + 8 KP (rows 8 swave + 64 KP ...), stage ST
             if (dma_s1) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs1, (pp_lptr_t)dst, 16, vo[KP], dma_sa, 0, 0);
             else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, (pp_lptr_t)dst, 16, vo[KP], dma_sa, 0, 0);
@@ -314,8 +307,8 @@ __global__ __launch_bounds__(512, 2) void conv_pp_kernel(ConvArgs a) {
 // Serves: split-fp16, 3x3, stride 1, NHWC out, both sources multiples of 32 channels and powers of two, N a multiple of 128, operands < 2 GiB.
 bool smirk_conv_pp_eligible(const ConvArgs& a) {
     const SmirkConvDesc& d = a.d;
-    const char* env = getenv("SMIRK_IGEMM_PP");                      // "0" keeps these layers on conv_igemm_kernel (A/B switch; read per call: tests toggle it)
-    if (env && env[0] == '0') return false;
+    const int mode = smirk_switch(SMIRK_SW_IGEMM_PP);                 // 0 keeps these layers on conv_igemm_kernel, 2 ("all") lifts the size limit below
+    if (mode == 0) return false;
     if (d.KH != 3 || d.KW != 3 || d.stride != 1 || d.out_mode != SMIRK_OUT_NHWC || d.pad_t != 1 || d.pad_l != 1) return false;
     if (d.Ho != d.H || d.Wo != d.W || d.W > 1023) return false;
     if (d.C0 % CV_BK || d.C1 % CV_BK || (d.C0 & (d.C0 - 1)) || (d.C1 & (d.C1 - 1))) return false;
@@ -326,26 +319,12 @@ bool smirk_conv_pp_eligible(const ConvArgs& a) {
     // (K = 2304 / 4608: 72 / 144 chunks per tile amortise the exposed prologue + epilogue of the single workgroup per CU), 28x28 and 56x56
     // layers 1-9 % SLOWER (36-72 chunks per tile; the 128x128 kernel hides one workgroup's epilogue behind its co-resident twin's main
     // loop).  SMIRK_IGEMM_PP=all lifts the restriction for experiments.
-    const bool all = env && env[0] == 'a';
-    if (!all && (long long)d.Ho * d.Wo > 256) return false;
+    if (mode != 2 && (long long)d.Ho * d.Wo > 256) return false;
     return a.M >= 4 * PP_BM;                                          // tiny problems stay on the 128-row tiles
 }
 
-int smirk_conv_pp_launch(const ConvArgs& a_in, hipStream_t st) {
-    static bool attr_done_dev[64] = {};                              // hipFuncSetAttribute is per-device state: one flag per device ordinal
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64) return SMIRK_ERR_UNSUPPORTED;
-    bool& attr_done = attr_done_dev[dev];
-    if (!attr_done) {
-        if (hipFuncSetAttribute((const void*)conv_pp_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_BYTES) != hipSuccess)
-            return SMIRK_ERR_LAUNCH;
-        attr_done = true;
-    }
-    ConvArgs a = a_in;
-#ifdef SMIRK_DEBUG_HOOKS                                                 /* -DSMIRK_DEBUG_HOOKS variant builds only (tools/build_variant.sh) */
-    if (const char* ab = getenv("SMIRK_PP_ABLATE")) a.ablate = atoi(ab);        // WRONG RESULTS: operand-traffic timing experiments
-#endif
+int smirk_conv_pp_launch(const ConvArgs& a, hipStream_t st) {
+    if (const int rc = smirk_raise_dynamic_lds((const void*)conv_pp_kernel<3>, PP_LDS_BYTES)) return rc;
     // NL = 3 of a wave's 6 LDS-DMA instructions per chunk are issued in its load phase, 3 among the MFMAs.  0 / 2 / 6 measured the same within 1 % (0.279-0.281 ms on
     // the 14 x 14 layer, profiles/r02_conv_pp_dma_split.txt); the $SMIRK_PP_NL switch and those instantiations left the library in round 5.
     const int ntm = (a.M + PP_BM - 1) / PP_BM, ntn = a.N / PP_BN;

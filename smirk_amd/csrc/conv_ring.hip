@@ -284,8 +284,7 @@ __global__ __launch_bounds__(256, TN == 1 ? 3 : 2) void conv3x3_ring_kernel(Ring
 // Serves: split-fp16, 3x3, stride 1, zero pad 1, same size, NHWC out, Cout = 64 (or Cout = 32 with >= 2 channel chunks: resident weights would leave one workgroup per CU), H, W multiples of 16 and >= 64, both sources whole power-of-two multiples of 32
 // channels, no residual, operands below 2 GiB (the dispatcher chunks larger batches).  $SMIRK_CONV_RING=0 restores the round-3 kernels (A/B switch, tests).
 bool smirk_conv3x3_ring64_eligible(const SmirkConvDesc* d, bool has_residual) {
-    const char* env = getenv("SMIRK_CONV_RING");                     // read per call: tests toggle it
-    if (env && env[0] == '0') return false;
+    if (!smirk_switch(SMIRK_SW_CONV_RING)) return false;
     if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad_t != 1 || d->pad_l != 1 || d->pad_mode != SMIRK_PAD_ZERO) return false;
     if (d->out_mode != SMIRK_OUT_NHWC || d->Ho != d->H || d->Wo != d->W || d->H % RG_PT || d->W % RG_PT || d->H < 64 || has_residual) return false;
     if ((d->Cout != 64 && !(d->Cout == 32 && d->C0 + d->C1 >= 64)) || d->C0 < 32 || d->C0 % 32 || d->C1 % 32 || (d->C0 & (d->C0 - 1)) || (d->C1 & (d->C1 - 1))) return false;
@@ -293,24 +292,15 @@ bool smirk_conv3x3_ring64_eligible(const SmirkConvDesc* d, bool has_residual) {
     return px * d->C0 * 4 < (1ll << 31) && px * d->C1 * 4 < (1ll << 31);
 }
 
+template <int TN, bool POOL, bool STATS = false>
+static int rg_launch(const RingArgs& a, int grid, hipStream_t st) {
+    if (const int rc = smirk_raise_dynamic_lds((const void*)conv3x3_ring_kernel<TN, POOL, STATS>, RG_LDS_BYTES(32 * TN))) return rc;
+    SMIRK_LAUNCH((conv3x3_ring_kernel<TN, POOL, STATS>), dim3(grid), dim3(256), RG_LDS_BYTES(32 * TN), st, a);
+    return smirk_launch_status();
+}
+
 int smirk_conv3x3_ring64_launch(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale, const float* shift, void* out,
                                 void* pooled, hipStream_t st, float* stats, int* stats_rows) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return SMIRK_ERR_LAUNCH;
-    static bool attr_done[64] = {};                                  // hipFuncSetAttribute is per-device state
-    static int n_cu[64] = {};
-    if (!attr_done[dev]) {
-        if (hipFuncSetAttribute((const void*)conv3x3_ring_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, RG_LDS_BYTES(64)) != hipSuccess ||
-            hipFuncSetAttribute((const void*)conv3x3_ring_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, RG_LDS_BYTES(64)) != hipSuccess ||
-            hipFuncSetAttribute((const void*)conv3x3_ring_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, RG_LDS_BYTES(32)) != hipSuccess ||
-            hipFuncSetAttribute((const void*)conv3x3_ring_kernel<2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, RG_LDS_BYTES(64)) != hipSuccess ||
-            hipFuncSetAttribute((const void*)conv3x3_ring_kernel<1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, RG_LDS_BYTES(32)) != hipSuccess)
-            return SMIRK_ERR_LAUNCH;
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        n_cu[dev] = cus;
-        attr_done[dev] = true;
-    }
     RingArgs a;
     a.in0 = (const float*)in0; a.in1 = (const float*)in1; a.w = (const float*)w; a.scale = scale; a.shift = shift;
     a.out = (float*)out; a.pool = (float*)pooled;
@@ -318,7 +308,8 @@ int smirk_conv3x3_ring64_launch(const SmirkConvDesc* d, const void* in0, const v
     a.nchunk = (d->C0 + d->C1) / 32;
     a.npatch = d->B * (d->H / RG_PT) * (d->W / RG_PT);
     const int per_cu = d->Cout == 32 ? 3 : 2;                        // resident workgroups per CU (LDS)
-    const int grid = a.npatch < per_cu * n_cu[dev] ? a.npatch : per_cu * n_cu[dev];
+    const int n_cu = smirk_device_cus();
+    const int grid = a.npatch < per_cu * n_cu ? a.npatch : per_cu * n_cu;
     a.stats = nullptr;
     if (stats && stats_rows && !pooled && !scale && !shift && d->act == SMIRK_ACT_NONE) { a.stats = stats; *stats_rows = grid * 4; }   // train mode: raw output + its column sums
     if (g_smirk_prof_on) {
@@ -326,13 +317,7 @@ int smirk_conv3x3_ring64_launch(const SmirkConvDesc* d, const void* in0, const v
         smirk_prof_next(d->Cout == 32 ? "conv3x3_ring_kernel<1>[16x16 patch,ring]" : pooled ? "conv3x3_ring_kernel<2,pool>[16x16 patch,ring]" : "conv3x3_ring_kernel<2>[16x16 patch,ring]",
                         2.0 * px * d->Cout * K, px * (d->C0 + d->C1) * 4.0 + px * d->Cout * 4.0 * (pooled ? 1.25 : 1.0) + K * d->Cout * 4.0);
     }
-    if (a.stats) {
-        if (d->Cout == 32) SMIRK_LAUNCH((conv3x3_ring_kernel<1, false, true>), dim3(grid), dim3(256), RG_LDS_BYTES(32), st, a);
-        else SMIRK_LAUNCH((conv3x3_ring_kernel<2, false, true>), dim3(grid), dim3(256), RG_LDS_BYTES(64), st, a);
-    } else if (d->Cout == 32) {
-        if (pooled) return SMIRK_ERR_UNSUPPORTED;
-        SMIRK_LAUNCH((conv3x3_ring_kernel<1, false>), dim3(grid), dim3(256), RG_LDS_BYTES(32), st, a);
-    } else if (pooled) SMIRK_LAUNCH((conv3x3_ring_kernel<2, true>), dim3(grid), dim3(256), RG_LDS_BYTES(64), st, a);
-    else SMIRK_LAUNCH((conv3x3_ring_kernel<2, false>), dim3(grid), dim3(256), RG_LDS_BYTES(64), st, a);
-    return smirk_launch_status();
+    if (a.stats) return d->Cout == 32 ? rg_launch<1, false, true>(a, grid, st) : rg_launch<2, false, true>(a, grid, st);
+    if (d->Cout == 32) return pooled ? SMIRK_ERR_UNSUPPORTED : rg_launch<1, false>(a, grid, st);
+    return pooled ? rg_launch<2, true>(a, grid, st) : rg_launch<2, false>(a, grid, st);
 }

@@ -24,7 +24,6 @@
 //
 // Bound: per patch 597 MFMAs (conv1 165 on 11 row tiles, conv2 432) = 4.8 k matrix-pipe cycles per CU against 9.9 GB / 1024 frames of HBM traffic
 // (~2 ms at 5 TB/s): MFMA / VALU co-bound, HBM close behind.  Algorithmic flop = 2 * B*H*W * 32 * (72 + 288).
-#include <stdlib.h>
 
 #include "conv_common.h"
 
@@ -56,17 +55,7 @@ struct Enc1Args {
     float *e1, *pool;
     int B, H, W;
     int npatch;            // B * (H/16) * (W/16)
-    long long* dbg;        // -DSMIRK_DEBUG_HOOKS variant builds only: phase time stamps [2 workgroups][2 groups][E1_DBG_IT][16] (tools/enc1_timeline.py)
 };
-#ifdef SMIRK_DEBUG_HOOKS
-#define E1_DBG_IT 24
-#define E1_STAMP(k)                                                                                                   \
-    do {                                                                                                              \
-        if (dbg_p && it < E1_DBG_IT) dbg_p[it * 16 + (k)] = (long long)__builtin_readcyclecounter();                   \
-    } while (0)
-#else
-#define E1_STAMP(k) do {} while (0)
-#endif
 
 typedef __attribute__((address_space(3))) void* e1_lptr_t;
 typedef const __attribute__((address_space(1))) void* e1_gptr_t;
@@ -259,10 +248,6 @@ __global__ __launch_bounds__(512, 2) void enc1_fused_kernel(Enc1Args a) {
     if (group == 1) __builtin_amdgcn_s_barrier();                    // group 1 runs one phase behind group 0
 #endif
 
-#ifdef SMIRK_DEBUG_HOOKS
-    const int dbg_blk = blockIdx.x == 0 ? 0 : blockIdx.x == 97 ? 1 : -1;
-    long long* const dbg_p = (a.dbg && dbg_blk >= 0 && wave == 0 && lane == 0) ? a.dbg + (size_t)(dbg_blk * 2 + group) * E1_DBG_IT * 16 : nullptr;
-#endif
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int it = 0; it < np_max; ++it) {
         const bool act = it < np_group;
@@ -271,7 +256,6 @@ __global__ __launch_bounds__(512, 2) void enc1_fused_kernel(Enc1Args a) {
         if (act) patch_origin(p, b, oy0, ox0);
 
         // ================= phase 0: conv1 (8 -> 32) on the 18 x 18 halo, two taps per k-step ============================================================
-        E1_STAMP(0);
         f32x16 acc0[3], acc1[3];
         if (act) {
             // address bases are made opaque at the start of the phase that uses them: whatever is derived from them (per-step sums, XOR variants) is then
@@ -306,13 +290,10 @@ __global__ __launch_bounds__(512, 2) void enc1_fused_kernel(Enc1Args a) {
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        E1_STAMP(1);
         __builtin_amdgcn_s_barrier();                                // every wave of the group has read XIN: it may be refilled
-        E1_STAMP(2);
 
         // ================= phase 1: conv1 epilogue: BN + ReLU, zero outside the image, split16 -> INT =================================
         if (act) {
-            E1_STAMP(10);
             f32x4 sc[4], sh[4];                                       // this lane's 16 channels (4 per group j): one LDS round trip per phase
 #pragma unroll
             for (int j = 0; j < 4; ++j) { sc[j] = *(const f32x4*)(coef + 0 + j * 8 + hb * 4); sh[j] = *(const f32x4*)(coef + 32 + j * 8 + hb * 4); }
@@ -353,14 +334,11 @@ __global__ __launch_bounds__(512, 2) void enc1_fused_kernel(Enc1Args a) {
                         }
                         E1_FENCE();
                     }
-                    E1_STAMP(11 + t);
                 }
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        E1_STAMP(3);
         __builtin_amdgcn_s_barrier();                                // INT is complete
-        E1_STAMP(4);
 
         // ================= phase 2: conv2 (32 -> 32) on the 16 x 16 patch from INT; wave w owns output rows 4 w .. 4 w + 3 =================================
         f32x16 d0[2], d1[2];
@@ -401,11 +379,8 @@ __global__ __launch_bounds__(512, 2) void enc1_fused_kernel(Enc1Args a) {
         }
         // the next patch's halo (requested at the start of this phase) has landed before anyone passes this barrier; no store of this wave is outstanding here
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        E1_STAMP(5);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        E1_STAMP(6);
         __builtin_amdgcn_s_barrier();                                // INT is dead: it becomes the per-wave output staging area
-        E1_STAMP(7);
 
         // ================= phase 3: conv2 epilogue: BN + ReLU -> e1 tile + pooled tile, staged through LDS, 1 KiB stores ====================================
         if (act) {
@@ -466,7 +441,6 @@ __global__ __launch_bounds__(512, 2) void enc1_fused_kernel(Enc1Args a) {
                     }
                     E1_FENCE();
                 }
-                if (i == 0) E1_STAMP(14);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // per-wave staging: LDS operations of one wave execute in order
                 const int oy = oy0 + 4 * wave + 2 * i;
                 // 64 lanes x 16 B = 8 consecutive pixels = 1 KiB per instruction: rows q*8 .. q*8+7 of the tile are pixels (q >> 1, (q & 1) * 8 ..) of the 2 x 16 tile;
@@ -483,13 +457,10 @@ __global__ __launch_bounds__(512, 2) void enc1_fused_kernel(Enc1Args a) {
                     *(uint4v*)o = val;
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // the staging area is rewritten by the next tile
-                if (i == 0) E1_STAMP(15);
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        E1_STAMP(8);
         __builtin_amdgcn_s_barrier();                                // staging reads done: INT may be written by the next patch's phase 1
-        E1_STAMP(9);
     }
 #if E1_PHASE_OFFSET
     if (group == 0) __builtin_amdgcn_s_barrier();                    // both groups have executed the same number of barriers
@@ -500,24 +471,15 @@ __global__ __launch_bounds__(512, 2) void enc1_fused_kernel(Enc1Args a) {
 // ---- host side ------------------------------------------------------------------------------------------------------------------------------------
 // Reference: src/smirk_generator.py:52-53 (enc1 = self.encoder1(x); self.pool1(enc1)), _block :88-119 (Conv2d 3x3 pad 1 bias=False, BatchNorm2d, ReLU, twice).
 extern "C" int smirk_enc1_fused_supported(int cin_pad, int features, int H, int W) {
-    return cin_pad == 8 && features == 32 && H >= E1_PT && W >= E1_PT && H % E1_PT == 0 && W % E1_PT == 0 && getenv("SMIRK_DISABLE_ENC1_FUSED") == nullptr;
+    return cin_pad == 8 && features == 32 && H >= E1_PT && W >= E1_PT && H % E1_PT == 0 && W % E1_PT == 0 && !smirk_switch(SMIRK_SW_DISABLE_ENC1_FUSED);
 }
 
 extern "C" int smirk_enc1_fused_split16(const void* x, const void* w1, const float* scale1, const float* shift1, const void* w2, const float* scale2,
                                         const float* shift2, void* e1, void* pooled, int B, int H, int W, void* stream) {
     if (!x || !w1 || !w2 || !scale1 || !shift1 || !scale2 || !shift2 || !e1 || !pooled || B <= 0) return SMIRK_ERR_BAD_ARG;
     if (H < E1_PT || W < E1_PT || H % E1_PT || W % E1_PT) return SMIRK_ERR_UNSUPPORTED;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return SMIRK_ERR_LAUNCH;
-    static bool attr_done[64] = {};                                  // hipFuncSetAttribute is per-device state
-    static int n_cu[64] = {};
-    if (!attr_done[dev]) {
-        if (hipFuncSetAttribute((const void*)enc1_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, E1_LDS_BYTES) != hipSuccess) return SMIRK_ERR_LAUNCH;
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        n_cu[dev] = cus;
-        attr_done[dev] = true;
-    }
+    if (const int rc = smirk_raise_dynamic_lds((const void*)enc1_fused_kernel, E1_LDS_BYTES)) return rc;
+    const int n_cu = smirk_device_cus();
     // the input halo goes through a buffer resource with 32-bit byte offsets: frames are independent, so larger batches run as chunks below 2 GiB of x
     const long long per_frame = (long long)H * W * 32;
     const int max_b = (int)(((1ll << 31) - 1) / per_frame);
@@ -532,12 +494,8 @@ extern "C" int smirk_enc1_fused_split16(const void* x, const void* w1, const flo
         a.pool = (float*)pooled + (size_t)b0 * (H / 2) * (W / 2) * 32;
         a.B = nb; a.H = H; a.W = W;
         a.npatch = nb * (H / E1_PT) * (W / E1_PT);
-        a.dbg = nullptr;
-#ifdef SMIRK_DEBUG_HOOKS                                                 /* a raw device address from the environment: variant builds only */
-        if (const char* e = getenv("SMIRK_ENC1_DBG")) a.dbg = (long long*)strtoull(e, nullptr, 16);
-#endif
         const int want = (a.npatch + 1) / 2;
-        const int grid = want < n_cu[dev] ? want : n_cu[dev];
+        const int grid = want < n_cu ? want : n_cu;
         if (g_smirk_prof_on) {
             const double px = (double)nb * H * W;
             smirk_prof_next("enc1_fused_kernel[conv8-32+conv32-32+pool]", 2.0 * px * 32.0 * (72.0 + 288.0), px * (32.0 + 128.0 + 32.0) + 4.0 * 32.0 * (72 + 288));

@@ -337,16 +337,7 @@ extern "C" int smirk_points_to_pixels(const float* points, int B, int L, int ima
 template <int R>
 static bool launch_maxpool_lds(const float* in, float* out, int B, int H, int W, int complement, hipStream_t st) {
     const size_t lds = (size_t)(MP_ROWS + 2 * R) * ((size_t)mp_row_stride(W, R) + W) * sizeof(float);
-    static bool attr_done[64] = {};                    // per device: the attribute is per-device state (one process may drive several GPUs)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-    if (!attr_done[dev]) {
-        if (hipFuncSetAttribute((const void*)maxpool_sq_lds_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;                              // not marked done: retried (and reported through the fallback) on the next call
-        }
-        attr_done[dev] = true;
-    }
+    if (smirk_raise_dynamic_lds((const void*)maxpool_sq_lds_kernel<R>, 160 * 1024) != SMIRK_OK) return false;   // retried on the next call
     const int tiles = (H + MP_ROWS - 1) / MP_ROWS;
     smirk_prof_next(nullptr, 0.0, 2.0 * B * H * W * sizeof(float));
     SMIRK_LAUNCH(maxpool_sq_lds_kernel<R>, dim3((unsigned)(B * tiles)), dim3(512), lds, st, in, out, H, W, complement & 1, (complement >> 1) & 1);

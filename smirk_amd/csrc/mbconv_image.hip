@@ -418,15 +418,7 @@ extern "C" int smirk_mbconv_image_supported(int H, int W, int Cin, int mid, int 
 
 template <int KS, int NT, bool TILE = false, bool PADK = false>
 static int mbi_launch(const MBIArgs& a, unsigned grid, size_t lds, hipStream_t st, double flop, double bytes) {
-    static bool attr_done[64] = {};                      // hipFuncSetAttribute is per-device state
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64) return SMIRK_ERR_UNSUPPORTED;
-    if (!attr_done[dev]) {
-        if (hipFuncSetAttribute((const void*)mbconv_image_kernel<KS, NT, TILE, PADK>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return SMIRK_ERR_LAUNCH;
-        attr_done[dev] = true;
-    }
+    if (const int rc = smirk_raise_dynamic_lds((const void*)mbconv_image_kernel<KS, NT, TILE, PADK>, 160 * 1024)) return rc;
     if (g_smirk_prof_on) {
         char nm[64];
         if (TILE || PADK) snprintf(nm, sizeof(nm), "mbconv_image_kernel<%d,%d,%s,%s>", KS, NT, TILE ? "true" : "false", PADK ? "true" : "false");

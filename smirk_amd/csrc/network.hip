@@ -144,16 +144,10 @@ extern "C" int smirk_generator_forward(const SmirkGeneratorWeights* w, const flo
     const int L0 = 3;
     int nchain = 1;
     if (B >= 2 && !taps && !g_smirk_prof_on) {                      // (taps copy whole tensors; the launch profiler times launches on ONE stream)
-        static int n_cu = 0;
-        if (n_cu == 0) {
-            int dev = 0, cus = 0;
-            if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) { (void)hipGetLastError(); cus = 256; }
-            n_cu = cus;
-        }
-        const double rounds = ((double)B * h16 * w16 / 256.0) * (c16 / 128.0) / n_cu;      // 256 x 128 tiles of a 14 x 14 layer per CU
+        const double rounds = ((double)B * h16 * w16 / 256.0) * (c16 / 128.0) / smirk_device_cus();      // 256 x 128 tiles of a 14 x 14 layer per CU
         const double full = (double)(long long)(rounds + 0.999999);
         if (B >= 16 && full > 0 && (full - rounds) / full > 0.05) nchain = 2;
-        if (const char* e = getenv("SMIRK_GEN_SPLIT_CHAINS")) nchain = e[0] == '0' ? 1 : e[0] == '3' ? 3 : 2;
+        if (const int forced = smirk_switch(SMIRK_SW_GEN_SPLIT_CHAINS)) nchain = forced;
         if (nchain > B) nchain = B;
     }
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -404,9 +398,9 @@ extern "C" int smirk_backbone_forward(const SmirkBackboneWeights* w, const float
     const BackbonePlan p = plan_backbone(w, B, H, W, ws);
     if (ws_bytes < p.total) return SMIRK_ERR_WORKSPACE;
     const bool split = w->precision == SMIRK_PRECISION_F16X3;
-    const bool no_image = getenv("SMIRK_DISABLE_MBCONV_IMAGE") != nullptr;                                                       // A/B switch (tests)
-    const bool no_tile = getenv("SMIRK_DISABLE_MBCONV_TILE") != nullptr;      // A/B switch (tests): the 24-48-channel blocks stay on mbconv_fused_kernel
-    const bool no_fuse = getenv("SMIRK_DISABLE_MBCONV_FUSED") != nullptr;                                                         // A/B switch (tests)
+    const bool no_image = smirk_switch(SMIRK_SW_DISABLE_MBCONV_IMAGE);                                                         // A/B switches (switches.h)
+    const bool no_tile = smirk_switch(SMIRK_SW_DISABLE_MBCONV_TILE);
+    const bool no_fuse = smirk_switch(SMIRK_SW_DISABLE_MBCONV_FUSED);
     const bool fuse_ds = false;       // DepthwiseSeparable blocks stay unfused (no expanded tensor to save: 202 vs 200 us at stride 1, 97 vs 66 at stride 2)
     int h = (H + 1) / 2, wd = (W + 1) / 2;
     void* x = p.rot.slot[0];
@@ -414,7 +408,7 @@ extern "C" int smirk_backbone_forward(const SmirkBackboneWeights* w, const float
     int first_block = 0;
     {
         const SmirkMbBlock& b0 = w->blocks[0];
-        const bool no_head = getenv("SMIRK_DISABLE_ENCODER_HEAD_FUSED") != nullptr;                                               // A/B switch (tests)
+        const bool no_head = smirk_switch(SMIRK_SW_DISABLE_ENCODER_HEAD_FUSED);
         if (split && !no_head && smirk_encoder_head_supported(w->stem_cout, b0.kind, b0.cin, b0.mid, b0.cout, b0.stride, b0.skip)) {
             TRY(smirk_encoder_head_fused_split16(img, (const float*)w->stem.w, w->stem.scale, w->stem.shift, (const float*)b0.dw.w, b0.dw.scale, b0.dw.shift,
                                                  b0.pw.w, b0.pw.scale, b0.pw.shift, b0.skip ? 1 : 0, x, B, H, W, b0.stride, stream));

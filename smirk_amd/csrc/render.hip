@@ -14,8 +14,6 @@
 //                      (925 MB at B=256 in the reference) + add_directionlight (renderer.py:239-250).
 //
 // Bound: HBM/L2 (integer + fp32 scan work).  Algorithmic bytes per face (image): verts in 60 KB, image out 602 KB.
-#include <atomic>
-#include <stdlib.h>
 
 #include "common.h"
 
@@ -227,7 +225,7 @@ __device__ __forceinline__ float wave_max(float v) {
 __global__ __launch_bounds__(256) void raster_tile(MeshDev m, int B, int H, int W, const float* __restrict__ frec,
                                                    const short4* __restrict__ fbox, const int* __restrict__ nvalid, const float* __restrict__ normals,
                                                    float* __restrict__ img, long long* __restrict__ p2f_out,
-                                                   float* __restrict__ bary_out, float* __restrict__ zbuf_out, int qmax, int ablate) {
+                                                   float* __restrict__ bary_out, float* __restrict__ zbuf_out, int qmax) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
     // layout: [FACE_CHUNK*FACE_REC floats][FACE_CHUNK ints][8 ints: per-wave list counts, 4 floats: per-wave block depth][4 x qmax uint16 lists]
     float* sface = (float*)dyn_smem;
@@ -244,7 +242,7 @@ __global__ __launch_bounds__(256) void raster_tile(MeshDev m, int B, int H, int 
     // ---- binning, order-preserving: wave w scans the sorted faces [w q, (w + 1) q) and compacts the ones whose box touches the tile into ITS list with a ballot
     // prefix (no atomics: the concatenation of the four lists is again in ascending zlow order)
     const short4* boxes = fbox + (size_t)b * m.Ff;
-    const int nv = (ablate & 2) ? 0 : nvalid[b];
+    const int nv = nvalid[b];
     {
         const int q = ((nv + 3) / 4 + 63) & ~63, lo = wave * q, hi = min(lo + q, nv);
         unsigned short* mylist = slist + wave * qmax;
@@ -271,7 +269,7 @@ __global__ __launch_bounds__(256) void raster_tile(MeshDev m, int B, int H, int 
     }
     __syncthreads();
     const int n0 = scnt[0], n1 = n0 + scnt[1], n2 = n1 + scnt[2];
-    const int n = (ablate & 1) ? 0 : n2 + scnt[3];
+    const int n = n2 + scnt[3];
 
     // a wave owns an 8 x 8 pixel block of the 32 x 8 tile (not a 32 x 2 strip): with face boxes of ~20 px the block is touched by 1.5x fewer faces
     const int xi = tx0 + (tid >> 6) * 8 + (tid & 7), yi = ty0 + ((tid & 63) >> 3);
@@ -486,27 +484,13 @@ extern "C" int smirk_render_forward(const SmirkRenderMesh* mesh, int B, int H, i
     const int tiles = ((W + TILE_W - 1) / TILE_W) * ((H + TILE_H - 1) / TILE_H);
     const int qmax = (((mesh->Ff + 3) / 4 + 63) & ~63) + 8;          // capacity of a wave's binned list (a quarter of the faces, whole 64-face rounds)
     const size_t smem = FACE_CHUNK * FACE_REC * 4 + FACE_CHUNK * 4 + 32 + smirk_align_up((size_t)4 * qmax * 2, 16);
-#ifdef SMIRK_DEBUG_HOOKS                                            /* -DSMIRK_DEBUG_HOOKS variant builds only (tools/build_variant.sh, tools/raster_time.py) */
-    static const char* abl = getenv("SMIRK_RASTER_ABLATE");      // 1: no per-pixel face loop, 2: no binning scan (timing experiments; wrong images)
-    const int ablate = abl ? atoi(abl) : 0;
-#else
-    const int ablate = 0;
-#endif
     if (smem > 64 * 1024) {
         // the four per-wave bin lists grow with the mesh (2 bytes per face): beyond ~27 k faces the dynamic LDS passes the 64 KB a launch gets by default.
-        // gfx950 has 160 KB per workgroup: raise this kernel's limit once per process (the largest size asked so far), refuse what cannot fit at all.
-        if (smem > 150 * 1024) return SMIRK_ERR_UNSUPPORTED;
-        static std::atomic<size_t> raised{0};
-        if (raised.load(std::memory_order_relaxed) < smem) {
-            if (hipFuncSetAttribute((const void*)raster_tile, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) {
-                (void)hipGetLastError();
-                return SMIRK_ERR_UNSUPPORTED;
-            }
-            raised.store(smem, std::memory_order_relaxed);
-        }
+        // gfx950 has 160 KB per workgroup: raise this kernel's limit on this device (the largest size asked so far), refuse what cannot fit at all.
+        if (smem > 150 * 1024 || smirk_raise_dynamic_lds((const void*)raster_tile, smem) != SMIRK_OK) return SMIRK_ERR_UNSUPPORTED;
     }
     SMIRK_LAUNCH(raster_tile, dim3(tiles, B), dim3(256), smem, st, d, B, H, W, frec, fbox, nvalid, nrm, img,
-                       (long long*)pix_to_face, bary, zbuf, qmax, ablate);
+                       (long long*)pix_to_face, bary, zbuf, qmax);
     return smirk_launch_status();
 }
 

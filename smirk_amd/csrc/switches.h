@@ -1,0 +1,45 @@
+// Environment switches of libsmirk_hip.so: the one place that names them and the one place that reads them (smirk_switch, capi.hip).
+// Each one chooses between kernel families for the same operation (A/B tests, integrators' bisection); every one is read on every call, so a test may set
+// and unset it between calls.
+//
+// variable                          values: what smirk_switch() returns, what it selects                                  default         used by
+// SMIRK_IGEMM_HALO                  "0": 0, deep 3x3 convolutions stay off conv_halo_kernel; anything else ("a..."          1               tests/test_conv_gpu.py
+//                                   included): 1, every eligible geometry on conv_halo_kernel
+// SMIRK_IGEMM_PP                    "0": 0, conv_pp_kernel off; "a...": 2, conv_pp_kernel for every eligible shape         1 (<= 16x16     tests/test_conv_gpu.py
+//                                   (not only images of at most 256 pixels); anything else: 1                             images)
+// SMIRK_CONV_RING                   "0": 0, the 64-output-channel ring kernels off (round-3 kernels); anything else: 1     1               tests/test_conv_gpu.py
+// SMIRK_DISABLE_PATCH_KERNEL        set (any value, "0" too): 1, neither the patch nor the ring convolution kernels        0               (integrators)
+// SMIRK_DISABLE_ENC1_FUSED          set (any value): 1, smirk_enc1_fused_supported answers 0                              0               tests/test_conv_gpu.py
+// SMIRK_DISABLE_MBCONV_IMAGE        set (any value): 1, no image-resident MBConv kernel in the encoder backbone           0               tests/test_encoder_gpu.py
+// SMIRK_DISABLE_MBCONV_TILE         set (any value): 1, the 24-48-channel stride-1 blocks stay on mbconv_fused_kernel     0               tests/test_encoder_gpu.py
+// SMIRK_DISABLE_MBCONV_FUSED        set (any value): 1, no fused MBConv kernels (separate expand / depthwise / project)   0               tests/test_encoder_gpu.py
+//                                   (smirk_encoder.py reads it too, for its own fused-block path)
+// SMIRK_DISABLE_ENCODER_HEAD_FUSED  set (any value): 1, stem and first block of the backbone as separate launches         0               tests/test_encoder_gpu.py
+// SMIRK_GEN_SPLIT_CHAINS            the number of the generator's H/8 + H/16 sub-batch chains: "0": 1, "3": 3, else 2     0 (unset):      tests/test_generator_gpu.py,
+//                                                                                                                         heuristic       bench.py
+// SMIRK_WGRAD_F16                   atoi(value): 0 exact-fp32 weight-gradient kernel, 1 / 2 split-fp16 x3 with 1 / 2       2               tests/test_train_ops_gpu.py
+//                                   chunks per barrier (+16: alternative LDS transpose lane geometry, diagnostic);                        (through smirk_conv_wgrad_
+//                                   smirk_conv_wgrad_set_mode overrides it                                                                set_mode)
+//
+// Switches read by the Python package, not here: SMIRK_AMD_*_PRECISION, SMIRK_ENCODER_SERIAL, SMIRK_ENCODER_TRAIN_SERIAL, SMIRK_BN_STATS_UNFUSED,
+// SMIRK_F16X3_RANGE_CHECK, SMIRK_HIP_LIBRARY.
+#pragma once
+
+#define SMIRK_WGRAD_F16_DEFAULT 2
+
+enum SmirkSwitch {
+    SMIRK_SW_IGEMM_HALO,
+    SMIRK_SW_IGEMM_PP,
+    SMIRK_SW_CONV_RING,
+    SMIRK_SW_DISABLE_PATCH_KERNEL,
+    SMIRK_SW_DISABLE_ENC1_FUSED,
+    SMIRK_SW_DISABLE_MBCONV_IMAGE,
+    SMIRK_SW_DISABLE_MBCONV_TILE,
+    SMIRK_SW_DISABLE_MBCONV_FUSED,
+    SMIRK_SW_DISABLE_ENCODER_HEAD_FUSED,
+    SMIRK_SW_GEN_SPLIT_CHAINS,
+    SMIRK_SW_WGRAD_F16,
+    SMIRK_SW_COUNT
+};
+
+int smirk_switch(SmirkSwitch s);

@@ -448,7 +448,6 @@ __global__ __launch_bounds__(256) void final_backward_kernel(const float* __rest
 #define WG_KC 16
 #define WG_LD 132
 #define WG_MAX_SPLIT 512
-#define SMIRK_WGRAD_F16_DEFAULT 2
 struct WgradArgs {
     const float *dz, *x;         // split16 [B][H][W][Cout], [B][H][W][Cin]
     float* part;
@@ -1279,13 +1278,12 @@ extern "C" int smirk_conv1x1_sigmoid_backward_split16(const float* dy, const flo
 static bool wgrad_halo_ok(int W, int Cout, int Cin, int KH, int reflect) {
     return KH == 3 && !reflect && W % 16 == 0 && (Cout == 32 || Cout == 64) && (Cin == 32 || Cin == 64);
 }
-// $SMIRK_WGRAD_F16: "0" = exact-fp32 MFMA kernel (wgrad_kernel), "1" / "2" = split-fp16 x3 kernel with 1 / 2 chunks per barrier (default 2);
+// $SMIRK_WGRAD_F16 (switches.h): "0" = exact-fp32 MFMA kernel (wgrad_kernel), "1" / "2" = split-fp16 x3 kernel with 1 / 2 chunks per barrier (default 2);
 // "+16" (17 / 18) selects the alternative lane geometry of the LDS transpose read (diagnostic)
 static int g_wgrad_mode_override = -1;
 static std::atomic<unsigned long long> g_wgrad_x1_fallbacks{0};
 static int wgrad_f16_mode() {
-    static const int mode = [] { const char* e = getenv("SMIRK_WGRAD_F16"); return e ? atoi(e) : SMIRK_WGRAD_F16_DEFAULT; }();
-    return g_wgrad_mode_override >= 0 ? g_wgrad_mode_override : mode;
+    return g_wgrad_mode_override >= 0 ? g_wgrad_mode_override : smirk_switch(SMIRK_SW_WGRAD_F16);
 }
 extern "C" int smirk_conv_wgrad_set_mode(int mode) {
     const int prev = wgrad_f16_mode();
