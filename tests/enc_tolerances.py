@@ -20,3 +20,9 @@ oneDNN / BLAS build), so a 2 x bound makes the suite flaky without any library b
 (5.9e-4 expected for independent errors on expression_params) on the fp32 side and 3.3x - 16x tighter than round 4's 2e-4 ... 1e-3 guesses everywhere else."""
 VS_FP32 = dict(pose_params=1.1e-5, cam=5e-5, shape_params=1.6e-4, expression_params=5e-4, eyelid_params=6e-5, jaw_params=3e-5)
 VS_FP64 = dict(pose_params=2.3e-5, cam=1.4e-4, shape_params=6.4e-4, expression_params=1.2e-3, eyelid_params=1.2e-4, jaw_params=8.4e-5)
+
+# Single MBConv blocks against float64 (tests/test_mbconv_block_gpu.py): every case is held to 4e-6 * max(1, max |ref|), the bound of
+# test_mbconv_image_kernel_vs_float64.  A case the fused kernel misses by rounding alone (no index pattern in the failure) gets at most twice the error the unfused
+# launch sequence shows on the same case against the same reference - both round D identically, the unfused path rounds E as well - recorded here as
+# (case id, runner) -> relative bound, with both measured maxima next to it.  No case needs an entry: all of them hold the 4e-6 bound (the test prints each case's figures before it asserts).
+BLOCK_VS_FP64 = {}
