@@ -543,6 +543,33 @@ int smirk_profile_stop(SmirkProfileRecord* out, int cap);
 int smirk_random_point_budget(int64_t* rbound, int B, int n_points, float mul, uint64_t seed, uint64_t offset, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Cycle path: the augmented FLAME parameters that start `step2` (smirk_trainer.py:192-248) in two launches on `stream`; no host
+ * synchronisation, no copy, no allocation.  Inputs are the encoder outputs, fp32 contiguous: expression [B][E], jaw [B][3], eyelid [B][2],
+ * shape [B][S], pose [B][3], cam [B][3].  Outputs have N = Ke * B rows; row r starts as input row r % B (torch.cat(Ke * [v])) and must not
+ * alias an input.  The N rows are split into four random groups (rank of a random key, cut at N/4, 2N/4, 3N/4):
+ *   group 0  e = clamp(n1 * (1 + 2u) * m + e0, -4, 4) + 0.2u' * n2       n1, n2 ~ N(0,1) and m ~ Bernoulli(1/2) per element, u, u' ~ U[0,1) per row
+ *   group 1  e = (0.25 + 1.25u) * e0[src] + 0.2u' * n                    src: a random permutation of the group's own rows
+ *   group 2  e[:num_expression] = (0.25 + 1.25u) * template, the other columns keep e0; then e += 0.2u' * n
+ *            template: a class drawn uniformly, then a row of that class uniformly
+ *   all      jaw += 0.2 * n * [1, .1, .1] * b, b ~ Bernoulli(1/2) per row; jaw[0] = clamp(jaw[0], 0, 0.5)
+ *            if use_eyelids: eyelid = clamp(eyelid + 0.25 * (2u - 1), 0, 1) per element
+ *   group 3  e = 0.2u' * n, jaw = 0, eyelid = u per element (whatever use_eyelids says)
+ * shape, pose and cam are copied.  plan [N][4] int32 = (group, position in the group, source row of group 1 or -1, template row of group 2 or -1).
+ * templates: device table [T][num_expression]; class_offsets: device int32 [n_classes + 1], rows of class c = [off[c], off[c+1]);
+ * class_offsets_host: the same numbers in host memory (validated before anything is launched: off[0] = 0, every class non-empty).
+ * Draws: Philox4x32-10 keyed by `seed`, counters from `offset`; a call consumes N * max(E, 4) counters (csrc/augment_rng.h has the layout).
+ * Errors, all before the device is touched: null pointer, B / Ke / E / S < 1, num_expression outside [1, E], no class or an empty class ->
+ * SMIRK_ERR_BAD_ARG; N > SMIRK_AUGMENT_MAX_ROWS -> SMIRK_ERR_UNSUPPORTED; ws_bytes below the workspace size of N -> SMIRK_ERR_WORKSPACE.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define SMIRK_AUGMENT_MAX_ROWS 8192
+size_t smirk_cycle_augment_workspace_bytes(int N);
+int smirk_cycle_augment(const float* expression, const float* jaw, const float* eyelid, const float* shape, const float* pose, const float* cam,
+                        int B, int E, int S, int Ke, int num_expression, int use_eyelids, const float* templates,
+                        const int32_t* class_offsets, const int32_t* class_offsets_host, int n_classes, uint64_t seed, uint64_t offset,
+                        float* out_expression, float* out_jaw, float* out_eyelid, float* out_shape, float* out_pose, float* out_cam,
+                        int32_t* plan, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Video loop pre/post-processing — replaces the cv2 / skimage calls of demo_video.py:107-214 so that a batch
  * of decoded frames stays in HBM from uint8 in to uint8 out.  uint8 images are HWC (cv2 layout), float images NCHW in [0,1].
  * ------------------------------------------------------------------------------------------------------------------ */

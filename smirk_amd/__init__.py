@@ -47,6 +47,7 @@ from .smirk_encoder import SmirkEncoder  # noqa: F401
 from .smirk_generator import SmirkGenerator  # noqa: F401
 from . import masking  # noqa: F401  (drop-in for src/utils/masking.py)
 from .video import VideoPipeline  # noqa: F401  (demo_video.py's frame loop, batched + streamed)
+from .augment import TemplateBank, augment_flame_params, load_templates  # noqa: F401  (smirk_trainer.py:192-248: the cycle path's augmented parameters)
 
 
 
@@ -58,4 +59,5 @@ def check_numerics():
     raise_if_range_tripped("smirk_amd.check_numerics", synchronize=True)
 
 
-__all__ = ["FLAME", "Renderer", "SmirkEncoder", "SmirkGenerator", "SmirkHipError", "lib", "masking", "VideoPipeline", "check_numerics"]
+__all__ = ["FLAME", "Renderer", "SmirkEncoder", "SmirkGenerator", "SmirkHipError", "lib", "masking", "VideoPipeline", "check_numerics", "TemplateBank", "augment_flame_params",
+           "load_templates"]

@@ -1,8 +1,11 @@
 """The compute of the reference trainer's cycle path (BASELINE config 5; smirk_trainer.py:184-332 `step2`, :349-382 `step`) over the smirk_amd modules.
 
-The trainer itself — parameter augmentation, dataset, logging, optimiser schedule — is the reference's and stays the reference's (caller of
-the hot path, out of scope).  What it asks of the four modules per step is restated here so that tests and bench.py can drive exactly that sequence:
+The trainer itself — dataset, logging, optimiser schedule — is the reference's and stays the reference's (caller of the hot path, out of
+scope).  The parameter augmentation that opens `step2` (smirk_trainer.py:192-248) is smirk_amd.augment (two HIP launches, no host synchronisation);
+`second_path` chains it with `render_second_path`.  What the trainer asks of the modules per step is restated here so that tests and bench.py can drive
+exactly that sequence:
 
+    augment_flame_params(encoder_output)      -> augmented params               smirk_trainer.py:192-248
     with no_grad:   FLAME(encoder_output), Renderer(...)                       smirk_trainer.py:247-249   (sampling of the source points)
                     FLAME(augmented params), Renderer(...)  -> rendered        smirk_trainer.py:252-254
                     mesh_based_mask_uniform_faces x2, transfer_pixels, mask    smirk_trainer.py:262-289
@@ -54,6 +57,17 @@ def render_second_path(flame, renderer, encoder_output, flame_feats, img, masks,
     masked_2nd = masking_utils.masking(img.repeat(Ke, 1, 1, 1), masks.repeat(Ke, 1, 1, 1), extra_points, mask_dilation_radius, rendered_mask=rendered_mask,
                                        extra_noise=True, random_mask=0.005)
     return rendered_2nd, masked_2nd
+
+
+def second_path(flame, renderer, encoder_output, bank, img, masks, face_probabilities, masking_utils, Ke=1, num_expression=50, use_eyelids=True,
+                mask_ratio=0.01, mask_dilation_radius=10, _rng_stream=None):
+    """smirk_trainer.py:192-291: the augmented parameters (smirk_amd.augment, `bank` = its TemplateBank) and everything between them and the generator's
+    input.  Returns (flame_feats, rendered, masked).  `_rng_stream` pins the augmentation's draws only; the masking draws follow torch's seed as always."""
+    from .augment import augment_flame_params
+    flame_feats = augment_flame_params(encoder_output, bank, Ke=Ke, num_expression=num_expression, use_eyelids=use_eyelids, _rng_stream=_rng_stream)
+    rendered, masked = render_second_path(flame, renderer, encoder_output, flame_feats, img, masks, face_probabilities, masking_utils, mask_ratio=mask_ratio,
+                                          mask_dilation_radius=mask_dilation_radius, Ke=Ke)
+    return flame_feats, rendered, masked
 
 
 def cycle_forward(generator, encoder, rendered, masked, flame_feats, freeze_generator=False, use_eyelids=True):
