@@ -570,6 +570,46 @@ int smirk_cycle_augment(const float* expression, const float* jaw, const float* 
                         int32_t* plan, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * First-path loss head (smirk_trainer.py:56-72, 97-101, 134-154; the cycle terms :304-313 are row terms too): up to SMIRK_LOSS_MAX_TERMS
+ * terms, their weighted total and its gradient.  Forward: two launches; backward: one; all on `stream`, no host synchronisation, no
+ * allocation, no copy, no atomics: two calls on the same inputs return the same bits.
+ *   SMIRK_LOSS_SQUARE     pred [rows][row_stride] against target (NULL = zeros): mean of (pred - target)^2 over the first `cols` columns of the
+ *                         rows whose byte in row_flags [rows] is non-zero (NULL = every row), i.e. F.mse_loss of the selected slice.  With no
+ *                         participating element the value is 0 and the gradient 0 (the trainer's Python int 0).  C, HW and loss_img unused (NULL).
+ *   SMIRK_LOSS_ABS_IMAGE  pred [rows][C][HW] against target (required): mean of |pred - target| over all elements, F.l1_loss.  row_stride = cols =
+ *                         C * HW, row_flags NULL.  loss_img (nullable) [rows][1][HW] = mean over C of |pred - target| (smirk_trainer.py:97-101).
+ * d = pred - target is taken in fp32 as torch takes it; d^2 / |d| are summed in float64, one partial per chunk of SMIRK_LOSS_CHUNK items (row
+ * term: elements of the slice; image term: pixels) in an order fixed by the shapes alone, the partials in index order.  out_terms [n_terms]:
+ * the unweighted fp32 terms as the trainer logs them; out_total [1] = sum of weight * term.
+ * Backward: reads the upstream gradient g of the total from the DEVICE pointer grad_total and, for every term whose `grad` is not NULL, writes
+ * grad [rows][row_stride] in full (zeros outside `cols` and in unflagged rows: the buffer may be uninitialised): g * weight * 2d / n for a
+ * squared term (evaluated in float64 from the fp32 operands and rounded once: it deliberately differs, by at most a few fp32 ulps, from torch's
+ * eager gradient, which takes d in fp32; the forward takes d in fp32 as torch does), g * weight * sign(d) / n with sign(0) = 0 for the image term.  Targets and flags are constants.  The workspace holds the
+ * forward's partials; the backward validates it and leaves it alone, so one buffer serves both and other calls may use it in between.
+ * Errors, all before the device is touched: NULL terms / pred / output / workspace, n_terms outside 1..SMIRK_LOSS_MAX_TERMS, rows / cols /
+ * row_stride < 1, cols > row_stride, unknown kind, image term with C < 1, HW < 1, C * HW != row_stride, cols != row_stride, flags or no target,
+ * loss_img on a squared term, pred / target / grad / loss_img / workspace not 16-byte aligned -> SMIRK_ERR_BAD_ARG; rows * row_stride above
+ * INT_MAX - SMIRK_LOSS_CHUNK -> SMIRK_ERR_UNSUPPORTED; ws_bytes below the workspace size -> SMIRK_ERR_WORKSPACE (the size query returns 0
+ * for terms the entries refuse).
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define SMIRK_LOSS_MAX_TERMS 8
+#define SMIRK_LOSS_CHUNK 4096
+#define SMIRK_LOSS_SQUARE 0
+#define SMIRK_LOSS_ABS_IMAGE 1
+typedef struct SmirkLossTerm {
+    const float* pred;
+    const float* target;
+    const uint8_t* row_flags;
+    int32_t rows, row_stride, cols, kind, C, HW;
+    float weight;
+    float* loss_img;
+    float* grad;
+} SmirkLossTerm;
+size_t smirk_loss_workspace_bytes(const SmirkLossTerm* terms, int n_terms);
+int smirk_loss_forward(const SmirkLossTerm* terms, int n_terms, float* out_terms, float* out_total, void* ws, size_t ws_bytes, void* stream);
+int smirk_loss_backward(const SmirkLossTerm* terms, int n_terms, const float* grad_total, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Video loop pre/post-processing — replaces the cv2 / skimage calls of demo_video.py:107-214 so that a batch
  * of decoded frames stays in HBM from uint8 in to uint8 out.  uint8 images are HWC (cv2 layout), float images NCHW in [0,1].
  * ------------------------------------------------------------------------------------------------------------------ */

@@ -11,7 +11,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libsmirk_hip.so")
 LIB_PATH = os.environ.get("SMIRK_HIP_LIBRARY", LIB_PATH)      # tuning aid: A/B a differently-built libsmirk_hip.so in one gpurun
-ABI_VERSION = 12
+ABI_VERSION = 13
 PACK_DEPTHWISE, PACK_STEM, PACK_CONVT2X2 = -3, -27, -2          # SmirkPackJob.KH markers (include/smirk_hip.h SMIRK_PACK_*)
 SMIRK_OK, SMIRK_ERR_BAD_ARG, SMIRK_ERR_WORKSPACE, SMIRK_ERR_LAUNCH, SMIRK_ERR_UNSUPPORTED = 0, -1, -2, -3, -4      # include/smirk_hip.h
 
@@ -64,6 +64,16 @@ class SmirkBackboneWeights(C.Structure):
 
 class SmirkProfileRecord(C.Structure):
     _fields_ = [("kernel", C.c_char * 120), ("flop", C.c_double), ("bytes", C.c_double), ("ms", C.c_float), ("_pad", C.c_int32)]
+
+
+LOSS_MAX_TERMS, LOSS_CHUNK = 8, 4096                            # include/smirk_hip.h SMIRK_LOSS_MAX_TERMS, SMIRK_LOSS_CHUNK
+LOSS_SQUARE, LOSS_ABS_IMAGE = 0, 1                               # SmirkLossTerm.kind
+
+
+class SmirkLossTerm(C.Structure):
+    _fields_ = [("pred", _p), ("target", _p), ("row_flags", _p)] + \
+               [(n, C.c_int32) for n in ("rows", "row_stride", "cols", "kind", "C", "HW")] + \
+               [("weight", C.c_float), ("loss_img", _p), ("grad", _p)]
 
 
 PAD_ZERO, PAD_REFLECT = 0, 1
@@ -175,6 +185,9 @@ _SIGS = {
     "smirk_random_point_budget": (_i, [_p, _i, _i, C.c_float, C.c_uint64, C.c_uint64, _p]),
     "smirk_cycle_augment_workspace_bytes": (_sz, [_i]),
     "smirk_cycle_augment": (_i, [_p] * 6 + [_i] * 6 + [_p, _p, _p, _i, C.c_uint64, C.c_uint64] + [_p] * 6 + [_p, _p, _sz, _p]),
+    "smirk_loss_workspace_bytes": (_sz, [C.POINTER(SmirkLossTerm), _i]),
+    "smirk_loss_forward": (_i, [C.POINTER(SmirkLossTerm), _i, _p, _p, _p, _sz, _p]),
+    "smirk_loss_backward": (_i, [C.POINTER(SmirkLossTerm), _i, _p, _p, _sz, _p]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -1,0 +1,70 @@
+"""The compute of the reference trainer's first path (smirk_trainer.py:34-154 `step1`) over the smirk_amd modules, the way smirk_amd.cycle restates `step2`.
+
+The trainer itself — dataset, logging, optimiser, the `.cpu()` copies of its visualisation dict — is the reference's and stays the reference's.  What
+`step1` asks of the modules, line by line:
+
+    encoder(batch['img'])                                       -> encoder_output        smirk_trainer.py:37
+    base_encoder(batch['img'])  (no_grad, optional)             -> base_output           smirk_trainer.py:40-41, 64-68
+    FLAME(encoder_output)                                       -> vertices, landmarks   smirk_trainer.py:43
+    Renderer(vertices, cam, landmarks_fan=, landmarks_mp=)      -> rendered, landmarks   smirk_trainer.py:46-49
+    masking.rendered_mask_of(rendered)                          -> rendered_mask         smirk_trainer.py:79
+    masking.mesh_based_mask_uniform_faces(transformed_vertices) -> npoints               smirk_trainer.py:83-86
+    masking.transfer_pixels(img, npoints, npoints)              -> extra_points          smirk_trainer.py:89
+    masking.masking(img, masks, extra_points, radius, rendered_mask)  -> masked_img      smirk_trainer.py:92
+    generator(cat[rendered, masked_img])                        -> reconstructed_img     smirk_trainer.py:94
+    FirstPathLoss (smirk_amd.losses)                            -> loss, terms, loss_img smirk_trainer.py:56-72, 97-101, 134-154
+    perceptual / emotion / MICA terms (:104-131)                -> `extra`: computed by the caller's networks, added by FirstPathLoss with their weights
+
+`forward_first_path` is everything up to the loss head, `first_path` adds the head.  Nothing here waits for the host: the terms stay on the device until
+the caller asks for `LossTerms.as_dict()`.
+"""
+import torch
+
+from . import masking as masking_utils
+
+
+def forward_first_path(encoder, flame, renderer, generator, batch, face_probabilities, enable_fuse_generator=True, mask_ratio=0.01, mask_dilation_radius=10,
+                       base_encoder=None, _rng_stream=None):
+    """smirk_trainer.py:37-49, 75-94.  Returns the outputs dict: encoder_output, base_output (None without a base encoder), vertices, rendered_img,
+    transformed_vertices, landmarks_fan, landmarks_mp and, with the generator, masked_1st_path and reconstructed_img.  `_rng_stream` (a
+    masking.PhiloxStream) pins the draws of the point sampling and of the masking noise; by default they follow torch's seed."""
+    img = batch['img']
+    encoder_output = encoder(img)
+    base_output = None
+    if base_encoder is not None:
+        with torch.no_grad():
+            base_output = base_encoder(img)
+    flame_output = flame.forward(encoder_output)
+    renderer_output = renderer.forward(flame_output['vertices'], encoder_output['cam'], landmarks_fan=flame_output['landmarks_fan'],
+                                       landmarks_mp=flame_output['landmarks_mp'])
+    rendered_img = renderer_output['rendered_img']
+    out = dict(encoder_output=encoder_output, base_output=base_output, vertices=flame_output['vertices'], rendered_img=rendered_img,
+               transformed_vertices=renderer_output['transformed_vertices'], landmarks_fan=renderer_output['landmarks_fan'],
+               landmarks_mp=renderer_output['landmarks_mp'])
+    if enable_fuse_generator:
+        rendered_mask = masking_utils.rendered_mask_of(rendered_img)
+        npoints, _ = masking_utils.mesh_based_mask_uniform_faces(renderer_output['transformed_vertices'], flame_faces=flame.faces_tensor,
+                                                                 face_probabilities=face_probabilities, mask_ratio=mask_ratio, _rng_stream=_rng_stream)
+        extra_points = masking_utils.transfer_pixels(img, npoints, npoints)
+        masked_img = masking_utils.masking(img, batch['mask'], extra_points, mask_dilation_radius, rendered_mask=rendered_mask, _rng_stream=_rng_stream)
+        out['masked_1st_path'] = masked_img
+        out['reconstructed_img'] = generator(torch.cat([rendered_img, masked_img], dim=1))
+    return out
+
+
+def first_path(encoder, flame, renderer, generator, loss, batch, face_probabilities, mask_ratio=0.01, mask_dilation_radius=10, base_encoder=None,
+               extra=None, _rng_stream=None):
+    """smirk_trainer.py:34-154.  `loss`: a smirk_amd.losses.FirstPathLoss (its enable_fuse_generator decides whether the generator runs); `batch`: 'img',
+    'mask', 'landmarks_fan', 'flag_landmarks_fan', 'landmarks_mp'; `base_encoder`: config.train.use_base_model_for_regularization; `extra`: a dict
+    {term name: scalar tensor} or a callable taking the outputs dict and returning one (the perceptual loss needs `reconstructed_img`).
+    Returns (loss_first_path, LossTerms, outputs dict); the outputs stay on the device."""
+    out = forward_first_path(encoder, flame, renderer, generator, batch, face_probabilities, enable_fuse_generator=loss.enable_fuse_generator,
+                             mask_ratio=mask_ratio, mask_dilation_radius=mask_dilation_radius, base_encoder=base_encoder, _rng_stream=_rng_stream)
+    if callable(extra):
+        extra = extra(out)
+    total, terms = loss(out['encoder_output'], out['landmarks_fan'], out['landmarks_mp'], batch, reconstructed_img=out.get('reconstructed_img'),
+                        base_output=out['base_output'], extra=extra)
+    out['img'], out['landmarks_fan_gt'], out['landmarks_mp_gt'] = batch['img'], batch['landmarks_fan'], batch['landmarks_mp']
+    if terms.loss_img is not None:
+        out['loss_img'] = terms.loss_img
+    return total, terms, out
