@@ -601,17 +601,48 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void conv_igemm_kernel(ConvArgs 
     conv_tile<BM, BN, WGM, WGN, SPLIT, KWALK, X1, STATS>(a, smem, mt * BM, nt * BN);
 }
 
-template <int BM, int BN, int WGM, int WGN, bool SPLIT, int KWALK, bool X1 = false>
-static void launch_igemm_kw(const ConvArgs& a, hipStream_t st) {
+// ---- host side: which instantiation serves a layer ---------------------------------------------------------------------------------
+// The ONE place that decides tile shape, K walk and whether the launch carries the STATS epilogue.  conv_dispatch_one launches from the plan and computes
+// *stats_rows from the same object, so the caller always reduces exactly the partial rows (one per M tile and wave row) that the kernel wrote.
+enum { TILE_128x128 = 0, TILE_128x64 = 1, TILE_256x32 = 2 };      // BM x BN; (WGM, WGN) = (2, 2), (2, 2), (4, 1)
+struct IgemmPlan { int tile; int kwalk; bool stats; int BM, WGM; };
+
+static IgemmPlan igemm_plan(const ConvArgs& a, bool split, bool /* x1: the one-MFMA product has the same instantiations and takes the same choices */, bool want_stats) {
+    const SmirkConvDesc& d = a.d;
+    IgemmPlan p;
+    if (a.N > 64) { p.tile = TILE_128x128; p.BM = 128; p.WGM = 2; }
+    else if (a.N > 32) { p.tile = TILE_128x64; p.BM = 128; p.WGM = 2; }
+    else { p.tile = TILE_256x32; p.BM = 256; p.WGM = 4; }
+    const bool c32 = d.C0 % CV_BK == 0 && d.C1 % CV_BK == 0;     // a chunk never straddles a tap or a concat source
+    const bool k3 = d.KH == 3 && d.KW == 3;
+    // channel-major walks: BN == 128 only (the 128 x 64 tile keeps the tap-major walk: DESIGN.md section 6, the channel-major instantiation of that tile).
+    // measured (B=128, same box, tap-major -> channel-major): 56x56 64->128 0.221 -> 0.201 ms, 128->128 0.367 -> 0.344, 256->128 0.725 -> 0.655;
+    // 28x28 128->256 0.203 -> 0.184, 256->256 0.357 -> 0.336, 512->256 0.680 -> 0.652; 14x14 layers unchanged; 112x112 64->64 (128x64 tile) 0.51 -> 0.54
+    const bool cm = split && p.tile == TILE_128x128 && k3 && c32;
+    if (split && c32 && conv_operands_fit32(a)) {
+        // buffer-addressed walks, default ON (measured, B=128, same box, old paths -> lean: 14x14x512 0.346 -> 0.327 ms, 28x28 512->256 0.665 -> 0.590, 56x56 256->128
+        // 0.715 -> 0.605, 112x112 64->64 0.50 -> 0.46); the pointer-based K walks below remain for operands the 32-bit buffer offsets cannot address
+        const bool pow2 = (d.C0 & (d.C0 - 1)) == 0 && (d.C1 & (d.C1 - 1)) == 0, even = ((d.C0 + d.C1) / CV_BK) % 2 == 0;
+        p.kwalk = (cm && pow2 && even) ? KW_LEAN_CM : KW_LEAN;
+    } else if (cm && d.Ho * d.Wo >= 400) p.kwalk = KW_CMAJOR;
+    else if (c32) p.kwalk = KW_FAST;
+    else if (d.KH * d.KW == 1) p.kwalk = KW_FAST_KT;
+    else p.kwalk = KW_GENERIC;
+    // the walks the training step's layers take are the ones with a STATS instantiation (split-fp16 only)
+    p.stats = want_stats && split && (p.kwalk == KW_LEAN || p.kwalk == KW_LEAN_CM || p.kwalk == KW_FAST_KT);
+    return p;
+}
+
+template <int BM, int BN, int WGM, int WGN, bool SPLIT, int KWALK, bool X1>
+static void launch_igemm_kw(const IgemmPlan& p, const ConvArgs& a, hipStream_t st) {
     const int ntm = (a.M + BM - 1) / BM, ntn = (a.N + BN - 1) / BN;
     if (g_smirk_prof_on) {                                       // the profiler's label is the instantiation that is launched HERE
         char nm[120];
         snprintf(nm, sizeof(nm), "conv_igemm_kernel<%d,%d,%d,%d,%s,%d>%s", BM, BN, WGM, WGN, SPLIT ? "true" : "false", KWALK, X1 ? "[f16x1]" : "");
-        const double px = (double)a.d.B * a.d.H * a.d.W;
-        smirk_prof_next(nm, 2.0 * a.M * a.N * a.K, 4.0 * (px * a.Cin + (double)a.M * a.N + (double)a.N * a.K + (a.residual ? (double)a.M * a.N : 0.0)));
+        conv_prof_next(nm, a);
     }
-    if constexpr (SPLIT && (KWALK == KW_LEAN || KWALK == KW_LEAN_CM || KWALK == KW_FAST_KT)) {      // the walks the training step's layers take
-        if (a.stats) {
+    if constexpr (SPLIT && (KWALK == KW_LEAN || KWALK == KW_LEAN_CM || KWALK == KW_FAST_KT)) {      // (igemm_plan sets `stats` for these walks only)
+        if (p.stats) {
             SMIRK_LAUNCH((conv_igemm_kernel<BM, BN, WGM, WGN, SPLIT, KWALK, X1, true>), dim3(ntm * ntn), dim3(64 * WGM * WGN), 0, st, a);
             return;
         }
@@ -619,58 +650,27 @@ static void launch_igemm_kw(const ConvArgs& a, hipStream_t st) {
     SMIRK_LAUNCH((conv_igemm_kernel<BM, BN, WGM, WGN, SPLIT, KWALK, X1>), dim3(ntm * ntn), dim3(64 * WGM * WGN), 0, st, a);
 }
 
-template <int BM, int BN, int WGM, int WGN, bool SPLIT, bool X1 = false>
-static void launch_igemm(const ConvArgs& a, hipStream_t st) {
-    const SmirkConvDesc& d = a.d;
-    // measured (B=128, same box, tap-major -> channel-major): 56x56 64->128 0.221 -> 0.201 ms, 128->128 0.367 -> 0.344, 256->128 0.725 -> 0.655;
-    // 28x28 128->256 0.203 -> 0.184, 256->256 0.357 -> 0.336, 512->256 0.680 -> 0.652; 14x14 layers unchanged; 112x112 64->64 (128x64 tile) 0.51 -> 0.54
-    // default ON (measured, B=128, same box, old paths -> lean: 14x14x512 0.346 -> 0.327 ms, 28x28 512->256 0.665 -> 0.590, 56x56 256->128
-    // 0.715 -> 0.605, 112x112 64->64 0.50 -> 0.46); the pointer-based K walks below remain for operands the 32-bit buffer offsets cannot address
-    const bool lean = true;
-    if constexpr (SPLIT && WGM * WGN == 4) {
-        const long long b0 = (long long)d.B * d.H * d.W * d.C0 * 4, b1 = (long long)d.B * d.H * d.W * d.C1 * 4, bw = (long long)a.N * a.K * 4;
-        if (lean && (d.C0 % CV_BK == 0) && (d.C1 % CV_BK == 0) && b0 < (1ll << 31) && b1 < (1ll << 31) && bw < (1ll << 31)) {
-            const bool pow2 = (d.C0 & (d.C0 - 1)) == 0 && (d.C1 & (d.C1 - 1)) == 0, even = ((d.C0 + d.C1) / CV_BK) % 2 == 0;
-            const bool want_cm = BN == 128;        // (the 128 x 64 tile keeps the tap-major lean walk: DESIGN.md section 6, the channel-major instantiation of that tile)
-            if (want_cm && d.KH == 3 && d.KW == 3 && pow2 && even) launch_igemm_kw<BM, BN, WGM, WGN, SPLIT, KW_LEAN_CM, X1>(a, st);
-            else launch_igemm_kw<BM, BN, WGM, WGN, SPLIT, KW_LEAN, X1>(a, st);
-            return;
-        }
+// the K walks that exist per tile: the buffer-addressed and channel-major ones are split-fp16 only
+template <int BM, int BN, int WGM, int WGN, bool SPLIT, bool X1>
+static void launch_igemm_tile(const IgemmPlan& p, const ConvArgs& a, hipStream_t st) {
+    switch (p.kwalk) {
+        case KW_LEAN_CM: if constexpr (SPLIT) launch_igemm_kw<BM, BN, WGM, WGN, SPLIT, KW_LEAN_CM, X1>(p, a, st); break;
+        case KW_LEAN: if constexpr (SPLIT) launch_igemm_kw<BM, BN, WGM, WGN, SPLIT, KW_LEAN, X1>(p, a, st); break;
+        case KW_CMAJOR: if constexpr (SPLIT) launch_igemm_kw<BM, BN, WGM, WGN, SPLIT, KW_CMAJOR, X1>(p, a, st); break;
+        case KW_FAST: launch_igemm_kw<BM, BN, WGM, WGN, SPLIT, KW_FAST, X1>(p, a, st); break;
+        case KW_FAST_KT: launch_igemm_kw<BM, BN, WGM, WGN, SPLIT, KW_FAST_KT, X1>(p, a, st); break;
+        default: launch_igemm_kw<BM, BN, WGM, WGN, SPLIT, KW_GENERIC, X1>(p, a, st); break;
     }
-    const bool cmajor = BN == 128 && d.Ho * d.Wo >= 400;
-    if constexpr (SPLIT && WGM * WGN == 4) {
-        if (cmajor && d.KH == 3 && d.KW == 3 && (d.C0 % CV_BK == 0) && (d.C1 % CV_BK == 0)) {
-            launch_igemm_kw<BM, BN, WGM, WGN, SPLIT, KW_CMAJOR, X1>(a, st);
-            return;
-        }
-    }
-    if ((d.C0 % CV_BK == 0) && (d.C1 % CV_BK == 0)) launch_igemm_kw<BM, BN, WGM, WGN, SPLIT, KW_FAST, X1>(a, st);
-    else if (d.KH * d.KW == 1) launch_igemm_kw<BM, BN, WGM, WGN, SPLIT, KW_FAST_KT, X1>(a, st);
-    else launch_igemm_kw<BM, BN, WGM, WGN, SPLIT, KW_GENERIC, X1>(a, st);
 }
 
-// conv_pp.hip: 8-wave ping-pong kernel (256 x 128 tile, 3-stage ring) for the deep split-fp16 3x3 layers
-bool smirk_conv_pp_eligible(const ConvArgs& a);
-int smirk_conv_pp_launch(const ConvArgs& a, hipStream_t st);
-
-// conv_halo.hip: the ping-pong schedule with the A operand staged once per channel chunk (one pixel halo serves all nine taps)
-bool smirk_conv_halo_eligible(const ConvArgs& a);
-int smirk_conv_halo_launch(const ConvArgs& a, hipStream_t st, bool x1);
-
-// conv_patch.hip: persistent halo-patch kernel for the large-image / few-channel 3x3 layers (split-fp16 only)
-bool smirk_conv3x3_patch_eligible(const SmirkConvDesc* d, bool has_residual);
-int smirk_conv3x3_patch_launch(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale,
-                               const float* shift, void* out, hipStream_t st, const float* fw, const float* fb, float* fout,
-                               int fcout);
-
-// conv_ring.hip: 16 x 16 patches, weights streamed through an LDS ring, two workgroups per CU (Cout = 64 at 112 x 112), optional fused 2 x 2 max-pool
-bool smirk_conv3x3_ring64_eligible(const SmirkConvDesc* d, bool has_residual);
-int smirk_conv3x3_ring64_launch(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale, const float* shift, void* out,
-                                void* pooled, hipStream_t st, float* stats = nullptr, int* stats_rows = nullptr);
-
-static int conv_dispatch_one(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale,
-                             const float* shift, const void* residual, void* out, void* stream, bool split, bool x1 = false, float* stats = nullptr,
-                             int* stats_rows = nullptr);
+template <bool SPLIT, bool X1>
+static void launch_igemm(const IgemmPlan& p, const ConvArgs& a, hipStream_t st) {
+    switch (p.tile) {
+        case TILE_128x128: launch_igemm_tile<128, 128, 2, 2, SPLIT, X1>(p, a, st); break;
+        case TILE_128x64: launch_igemm_tile<128, 64, 2, 2, SPLIT, X1>(p, a, st); break;
+        default: launch_igemm_tile<256, 32, 4, 1, SPLIT, X1>(p, a, st); break;
+    }
+}
 
 // The buffer-addressed operand DMA of the split-fp16 kernels (32-bit per-lane offsets, out-of-range rows as the zero padding) needs every
 // input tensor below 2 GiB.  A whole 1024-frame shard in one pass exceeds that on the 224^2 / 112^2 layers (6.6 / 3.3 GB): such a layer is
@@ -678,28 +678,27 @@ static int conv_dispatch_one(const SmirkConvDesc* d, const void* in0, const void
 // (tests/test_scale_gpu.py), so this is the same computation, and each chunk still holds >= 10^4 tiles.  Returns the images per launch.
 static int conv_batch_chunk(const SmirkConvDesc* d, bool split) {
     if (!split || d->B <= 1) return d->B;
-    const long long px = (long long)d->H * d->W, per = 4 * px * (d->C0 > d->C1 ? d->C0 : d->C1), lim = (1ll << 31) - 1;
-    if (per * d->B <= lim || per > lim) return d->B;
-    return (int)(lim / per);
+    const long long per = (long long)d->H * d->W * (d->C0 > d->C1 ? d->C0 : d->C1);          // dwords per image of the larger input
+    if (conv_fits32(per * d->B) || !conv_fits32(per)) return d->B;
+    return (int)((CONV_BUF_LIMIT - 1) / (4 * per));
 }
 
-static int conv_dispatch(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale,
-                         const float* shift, const void* residual, void* out, void* stream, bool split, bool x1 = false, float* stats = nullptr,
-                         int* stats_rows = nullptr) {
-    if (!d || !in0 || !w || !out) return SMIRK_ERR_BAD_ARG;
-    if (stats_rows) *stats_rows = 0;                            // (a layer run as several batch chunks writes no statistics: the caller reduces the stored tensor)
-    const int bc = (d->B > 0 && d->H > 0 && d->W > 0 && d->C0 > 0 && d->C1 >= 0) ? conv_batch_chunk(d, split) : d->B;
-    if (bc >= d->B) return conv_dispatch_one(d, in0, in1, w, scale, shift, residual, out, stream, split, x1, stats, stats_rows);
+// One batch chunk of a layer: its descriptor, its first image, and the dword offsets of that image in in0 / in1 / the layer's own output (and residual).
+struct ConvChunk { SmirkConvDesc d; int b0; size_t in0, in1, out; };
+
+// Runs launch(chunk) -> rc over the chunks of `bc` images of *d, in order; stops at the first chunk that does not return SMIRK_OK.
+template <typename Launch>
+static int conv_for_batch_chunks(const SmirkConvDesc* d, int bc, Launch launch) {
     const size_t ipx = (size_t)d->H * d->W, opx = (size_t)d->Ho * d->Wo * (d->out_mode == SMIRK_OUT_CONVT2X2 ? 4 : 1);
     for (int b0 = 0; b0 < d->B; b0 += bc) {
-        SmirkConvDesc dc = *d;
-        dc.B = d->B - b0 < bc ? d->B - b0 : bc;
-        const int rc = conv_dispatch_one(&dc, (const float*)in0 + b0 * ipx * d->C0, in1 ? (const float*)in1 + b0 * ipx * d->C1 : nullptr, w, scale, shift,
-                                         residual ? (const float*)residual + b0 * opx * d->Cout : nullptr, (float*)out + b0 * opx * d->Cout, stream, split, x1);
+        ConvChunk c = {*d, b0, b0 * ipx * d->C0, b0 * ipx * d->C1, b0 * opx * d->Cout};
+        c.d.B = d->B - b0 < bc ? d->B - b0 : bc;
+        const int rc = launch(c);
         if (rc != SMIRK_OK) return rc;
     }
     return SMIRK_OK;
 }
+static const float* chunk_ptr(const void* p, size_t off) { return p ? (const float*)p + off : nullptr; }
 
 static int conv_dispatch_one(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale,
                              const float* shift, const void* residual, void* out, void* stream, bool split, bool x1, float* stats, int* stats_rows) {
@@ -730,45 +729,41 @@ static int conv_dispatch_one(const SmirkConvDesc* d, const void* in0, const void
     if (d->KH == 3)                                             // only convs with a halo profit from patch ordering
         while (a.psh < 4 && d->Ho % (2 << a.psh) == 0 && d->Wo % (2 << a.psh) == 0) ++a.psh;
     hipStream_t st = (hipStream_t)stream;
-    const bool no_patch = smirk_switch(SMIRK_SW_DISABLE_PATCH_KERNEL);         // A/B switch: neither the patch nor the ring kernels
-    // F16X1 lives in conv_igemm_kernel only: the specialised kernels below issue the three-MFMA product unconditionally
-    if (split && !x1 && !no_patch && smirk_conv3x3_ring64_eligible(d, residual != nullptr))         // conv_ring.hip: the 64-output-channel layers on large images
-        return smirk_conv3x3_ring64_launch(d, in0, in1, w, scale, shift, out, nullptr, st, stats, stats_rows);      // (they write statistics only for a raw epilogue)
-    if (split && !x1 && !no_patch && smirk_conv3x3_patch_eligible(d, residual != nullptr))
+
+    // Kernel family, first match wins: ring -> patch -> halo -> ping-pong -> implicit GEMM.  Every family reads its own switch, once per launch.
+    // F16X1 lives in conv_igemm_kernel and conv_halo_x1_kernel only: the other specialised kernels issue the three-MFMA product unconditionally.
+    const bool f16x3 = split && !x1;
+    const bool patch_ok = !smirk_switch(SMIRK_SW_DISABLE_PATCH_KERNEL) && f16x3;         // A/B switch: neither the patch nor the ring kernels
+    if (patch_ok && smirk_conv3x3_ring64_eligible(d, residual != nullptr))               // the 64-output-channel layers on large images
+        return smirk_conv3x3_ring64_launch(d, in0, in1, w, scale, shift, out, nullptr, st, stats, stats_rows);      // (writes statistics, and its row count, only for a raw epilogue)
+    if (patch_ok && smirk_conv3x3_patch_eligible(d, residual != nullptr))                // (no statistics epilogue: conv_patch.hip)
         return smirk_conv3x3_patch_launch(d, in0, in1, w, scale, shift, out, st, nullptr, nullptr, nullptr, 0);
     // train mode: BatchNorm statistics of the RAW output from the accumulators (ConvArgs::stats), for the kernel families that carry the STATS epilogue
     const bool want_stats = split && stats && stats_rows && d->out_mode == SMIRK_OUT_NHWC && !scale && !shift && !residual && d->act == SMIRK_ACT_NONE;
-    if (split && smirk_conv_halo_eligible(a)) {                    // (the halo kernel has an X1 instantiation: conv_halo_x1_kernel)
-        if (want_stats) { a.stats = stats; *stats_rows = ((a.M + 255) / 256) * 4; }            // 256-row tiles x 4 wave rows
+    if (split && smirk_conv_halo_eligible(a)) {
+        if (want_stats) { a.stats = stats; *stats_rows = ((a.M + HS_BM - 1) / HS_BM) * HS_WGM; }
         return smirk_conv_halo_launch(a, st, x1);
     }
-    if (split && !x1 && smirk_conv_pp_eligible(a)) return smirk_conv_pp_launch(a, st);
-    if (want_stats) {
-        // the K walks launch_igemm picks for operands below 2 GiB (KW_LEAN / KW_LEAN_CM when
-        // every source has C % 32 == 0, KW_FAST_KT for 1x1 layers otherwise) carry the STATS epilogue; one partial row per (M tile, wave row)
-        const long long b0 = (long long)d->B * d->H * d->W * d->C0 * 4, b1 = (long long)d->B * d->H * d->W * d->C1 * 4, bw = (long long)a.N * a.K * 4;
-        const bool lean = (d->C0 % CV_BK == 0) && (d->C1 % CV_BK == 0) && b0 < (1ll << 31) && b1 < (1ll << 31) && bw < (1ll << 31);
-        const bool kt = !((d->C0 % CV_BK == 0) && (d->C1 % CV_BK == 0)) && d->KH * d->KW == 1;
-        if (lean || kt) {
-            const int BMt = a.N > 32 ? 128 : 256, WGMt = a.N > 32 ? 2 : 4;
-            a.stats = stats;
-            *stats_rows = ((a.M + BMt - 1) / BMt) * WGMt;
-        }
-    }
-    if (split && x1) {                                           // F16X1: the same three tile shapes, one MFMA per block
-        if (a.N > 64) launch_igemm<128, 128, 2, 2, true, true>(a, st);
-        else if (a.N > 32) launch_igemm<128, 64, 2, 2, true, true>(a, st);
-        else launch_igemm<256, 32, 4, 1, true, true>(a, st);
-    } else if (split) {
-        if (a.N > 64) launch_igemm<128, 128, 2, 2, true>(a, st);
-        else if (a.N > 32) launch_igemm<128, 64, 2, 2, true>(a, st);
-        else launch_igemm<256, 32, 4, 1, true>(a, st);
-    } else {
-        if (a.N > 64) launch_igemm<128, 128, 2, 2, false>(a, st);
-        else if (a.N > 32) launch_igemm<128, 64, 2, 2, false>(a, st);
-        else launch_igemm<256, 32, 4, 1, false>(a, st);
-    }
+    if (f16x3 && smirk_conv_pp_eligible(a)) return smirk_conv_pp_launch(a, st);       // (no statistics epilogue)
+    const IgemmPlan p = igemm_plan(a, split, x1, want_stats);
+    if (p.stats) { a.stats = stats; *stats_rows = ((a.M + p.BM - 1) / p.BM) * p.WGM; }
+    if (split && x1) launch_igemm<true, true>(p, a, st);        // F16X1: the same three tile shapes, one MFMA per block
+    else if (split) launch_igemm<true, false>(p, a, st);
+    else launch_igemm<false, false>(p, a, st);
     return smirk_launch_status();
+}
+
+static int conv_dispatch(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale,
+                         const float* shift, const void* residual, void* out, void* stream, bool split, bool x1 = false, float* stats = nullptr,
+                         int* stats_rows = nullptr) {
+    if (!d || !in0 || !w || !out) return SMIRK_ERR_BAD_ARG;
+    if (stats_rows) *stats_rows = 0;                            // (a layer run as several batch chunks writes no statistics: the caller reduces the stored tensor)
+    const int bc = (d->B > 0 && d->H > 0 && d->W > 0 && d->C0 > 0 && d->C1 >= 0) ? conv_batch_chunk(d, split) : d->B;
+    if (bc >= d->B) return conv_dispatch_one(d, in0, in1, w, scale, shift, residual, out, stream, split, x1, stats, stats_rows);
+    return conv_for_batch_chunks(d, bc, [&](const ConvChunk& c) {
+        return conv_dispatch_one(&c.d, (const float*)in0 + c.in0, chunk_ptr(in1, c.in1), w, scale, shift, chunk_ptr(residual, c.out), (float*)out + c.out, stream,
+                                 split, x1, nullptr, nullptr);
+    });
 }
 
 extern "C" int smirk_conv_igemm_f32(const SmirkConvDesc* d, const float* in0, const float* in1, const float* w,
@@ -792,15 +787,10 @@ extern "C" int smirk_conv3x3_pool_f16x3(const SmirkConvDesc* d, const void* in0,
         d0.B = d->B < bc ? d->B : bc;
         if (d0.Cout != 64 || !smirk_conv3x3_ring64_eligible(&d0, false)) return SMIRK_ERR_UNSUPPORTED;
     }
-    const size_t px = (size_t)d->H * d->W;
-    for (int b0 = 0; b0 < d->B; b0 += bc) {
-        SmirkConvDesc dc = *d;
-        dc.B = d->B - b0 < bc ? d->B - b0 : bc;
-        const int rc = smirk_conv3x3_ring64_launch(&dc, (const float*)in0 + b0 * px * d->C0, in1 ? (const float*)in1 + b0 * px * d->C1 : nullptr, w, scale, shift,
-                                                   (float*)out + b0 * px * d->Cout, (float*)pooled + b0 * (px / 4) * d->Cout, (hipStream_t)stream);
-        if (rc != SMIRK_OK) return rc;
-    }
-    return SMIRK_OK;
+    return conv_for_batch_chunks(d, bc, [&](const ConvChunk& c) {       // (same-size output, H and W even: the pooled tensor is a quarter of it)
+        return smirk_conv3x3_ring64_launch(&c.d, (const float*)in0 + c.in0, chunk_ptr(in1, c.in1), w, scale, shift, (float*)out + c.out, (float*)pooled + c.out / 4,
+                                           (hipStream_t)stream);
+    });
 }
 
 extern "C" int smirk_conv3x3_tail_f16x3(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale,
@@ -811,15 +801,10 @@ extern "C" int smirk_conv3x3_tail_f16x3(const SmirkConvDesc* d, const void* in0,
     if (!smirk_conv3x3_patch_eligible(d, false)) return SMIRK_ERR_UNSUPPORTED;
     const int bc = (d->B > 0 && d->H > 0 && d->W > 0 && d->C0 > 0 && d->C1 >= 0) ? conv_batch_chunk(d, true) : d->B;
     if (bc >= d->B) return smirk_conv3x3_patch_launch(d, in0, in1, w, scale, shift, nullptr, (hipStream_t)stream, fw, fb, out_nchw, fcout);
-    const size_t px = (size_t)d->H * d->W;
-    for (int b0 = 0; b0 < d->B; b0 += bc) {                     // batch chunks below 2 GiB each (see conv_batch_chunk)
-        SmirkConvDesc dc = *d;
-        dc.B = d->B - b0 < bc ? d->B - b0 : bc;
-        const int rc = smirk_conv3x3_patch_launch(&dc, (const float*)in0 + b0 * px * d->C0, in1 ? (const float*)in1 + b0 * px * d->C1 : nullptr, w, scale, shift,
-                                                  nullptr, (hipStream_t)stream, fw, fb, out_nchw + b0 * px * fcout, fcout);
-        if (rc != SMIRK_OK) return rc;
-    }
-    return SMIRK_OK;
+    return conv_for_batch_chunks(d, bc, [&](const ConvChunk& c) {       // (the NCHW output has its own stride per image)
+        return smirk_conv3x3_patch_launch(&c.d, (const float*)in0 + c.in0, chunk_ptr(in1, c.in1), w, scale, shift, nullptr, (hipStream_t)stream, fw, fb,
+                                          out_nchw + (size_t)c.b0 * d->H * d->W * fcout, fcout);
+    });
 }
 
 extern "C" int smirk_conv_igemm_f16x3(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w,
@@ -890,8 +875,6 @@ extern "C" int smirk_split16_to_f32(const void* in, float* out, size_t n_elems, 
     SMIRK_LAUNCH(split16_to_f32_kernel, dim3(grid_for(n_elems / 8, 16384)), dim3(256), 0, (hipStream_t)stream, (const float*)in, out, n_elems / 8);
     return smirk_launch_status();
 }
-
-static unsigned grid_for(size_t total, unsigned cap);
 
 // Range audit of a split16 tensor (debugging aid behind $SMIRK_F16X3_RANGE_CHECK): the split-fp16 format carries |x| < 65504 only (hi is an fp16);
 // counts the values whose hi half is non-finite or whose magnitude reaches `limit`.  counts[0] += offenders, counts[1] = max |x| seen (as float bits).

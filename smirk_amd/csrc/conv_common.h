@@ -1,5 +1,6 @@
-// Shared pieces of the implicit-GEMM convolution kernels (conv.hip, conv_pp.hip): argument block, GEMM-row -> pixel map, the split-fp16
-// conversions and the XOR-swizzled LDS operand image.  See conv.hip for the design notes.
+// Shared pieces of the convolution kernels (conv.hip and the conv_*.hip units it dispatches to): argument block, GEMM-row -> pixel map, the split-fp16
+// conversions, the XOR-swizzled LDS operand image, the operand-size predicate of the buffer-addressed loads and the cross-unit launcher prototypes.
+// See conv.hip for the design notes.
 #pragma once
 #include "common.h"
 
@@ -13,8 +14,8 @@ struct ConvArgs {
     float* out;
     int M, N, K, Cin;
     float* stats;  // train mode (BatchNorm statistics from the accumulators): per-tile partial column sums [rows][N][2] = (sum z, sum z^2) in fp32, or nullptr.
-                   // Every kernel family that honours it states its row count through smirk_conv_stats_rows(); the fixed-order fp64 reduction over the rows is
-                   // bn_finalize_partials_kernel (train.hip)
+                   // Whoever fixes a launch's geometry states its row count next to it (conv_dispatch_one, smirk_conv3x3_ring64_launch); the fixed-order fp64
+                   // reduction over the rows is bn_finalize_partials_kernel (train.hip)
     int psh;       // GEMM rows enumerate each image in (2^psh x 2^psh)-pixel patches (tile-major): a BM-row tile is then a compact 2-D
                    // patch whose 3x3 halo is ~1.3x its area instead of 3 full image rows — the im2col re-reads stay in L1/L2
 };
@@ -81,3 +82,43 @@ __device__ __forceinline__ int xcd_logical(int id, int nblk) {
     const int q = nblk >> 3, r = nblk & 7;
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
 }
+
+// ---- host side ------------------------------------------------------------------------------------------------------------------
+// Buffer-addressed operand DMA (`buffer_load_dwordx4 ... offen lds`) reaches a tensor through 32-bit byte offsets and a 32-bit num_records: the tensor must
+// end below 2 GiB.  `dwords` = its size in 4-byte elements (fp32, or split-fp16 pairs).
+#define CONV_BUF_LIMIT (1ll << 31)
+static inline bool conv_fits32(long long dwords) { return dwords * 4 < CONV_BUF_LIMIT; }
+// both activation sources of a layer
+static inline bool conv_inputs_fit32(const SmirkConvDesc& d) {
+    const long long px = (long long)d.B * d.H * d.W;
+    return conv_fits32(px * d.C0) && conv_fits32(px * d.C1);
+}
+// in0 / in1 / w of an implicit GEMM
+static inline bool conv_operands_fit32(const ConvArgs& a) { return conv_inputs_fit32(a.d) && conv_fits32((long long)a.N * a.K); }
+
+// the launch profiler's algorithmic work of an implicit GEMM (common.h smirk_prof_next): 2 M N K flop; every operand, the output and the residual once
+static inline void conv_prof_next(const char* name, const ConvArgs& a) {
+    if (!g_smirk_prof_on) return;
+    const double px = (double)a.d.B * a.d.H * a.d.W;
+    smirk_prof_next(name, 2.0 * a.M * a.N * a.K, 4.0 * (px * a.Cin + (double)a.M * a.N + (double)a.N * a.K + (a.residual ? (double)a.M * a.N : 0.0)));
+}
+
+// The kernel families conv_dispatch_one (conv.hip) tries before conv_igemm_kernel, in this order.  A family that writes ConvArgs::stats has its partial-row
+// count computed by whoever fixes its launch geometry.
+// conv_ring.hip: 16 x 16 patches, weights streamed through an LDS ring, two workgroups per CU (Cout = 64 at 112 x 112), optional fused 2 x 2 max-pool
+bool smirk_conv3x3_ring64_eligible(const SmirkConvDesc* d, bool has_residual);
+int smirk_conv3x3_ring64_launch(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale, const float* shift, void* out,
+                                void* pooled, hipStream_t st, float* stats = nullptr, int* stats_rows = nullptr);
+// conv_patch.hip: persistent halo-patch kernel for the large-image / few-channel 3x3 layers (split-fp16 only)
+bool smirk_conv3x3_patch_eligible(const SmirkConvDesc* d, bool has_residual);
+int smirk_conv3x3_patch_launch(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale,
+                               const float* shift, void* out, hipStream_t st, const float* fw, const float* fb, float* fout,
+                               int fcout);
+// conv_halo.hip: the ping-pong schedule with the A operand staged once per channel chunk (one pixel halo serves all nine taps); 256-row tiles x 4 wave rows
+#define HS_BM 256
+#define HS_WGM 4
+bool smirk_conv_halo_eligible(const ConvArgs& a);
+int smirk_conv_halo_launch(const ConvArgs& a, hipStream_t st, bool x1);
+// conv_pp.hip: 8-wave ping-pong kernel (256 x 128 tile, 3-stage ring) for the deep split-fp16 3x3 layers
+bool smirk_conv_pp_eligible(const ConvArgs& a);
+int smirk_conv_pp_launch(const ConvArgs& a, hipStream_t st);

@@ -23,8 +23,7 @@
 
 #include "conv_common.h"
 
-#define HS_BM 256
-#define HS_BN 128
+#define HS_BN 128                               /* HS_BM (256) and the 4 wave rows HS_WGM: conv_common.h, the dispatcher sizes the statistics rows from them */
 #define HS_NSTAGE 3
 #define HS_BRING_BYTES (HS_NSTAGE * HS_BN * 128) /* 49,152 B */
 #define HS_EPI_LD (2 * 32 + 4)
@@ -370,8 +369,7 @@ bool smirk_conv_halo_eligible(const ConvArgs& a) {
     if (d.Ho != d.H || d.Wo != d.W || d.W > 63 || d.W < 2 || d.H < 2) return false;
     if (d.C0 % CV_BK || d.C1 % CV_BK || (d.C0 & (d.C0 - 1)) || (d.C1 & (d.C1 - 1))) return false;
     if (a.N % HS_BN || a.N < HS_BN) return false;
-    const long long b0 = (long long)d.B * d.H * d.W * d.C0 * 4, b1 = (long long)d.B * d.H * d.W * d.C1 * 4, bw = (long long)a.N * a.K * 4;
-    if (b0 >= (1ll << 31) || b1 >= (1ll << 31) || bw >= (1ll << 31)) return false;
+    if (!conv_operands_fit32(a)) return false;
     if (a.M < 4 * HS_BM) return false;                               // tiny problems stay on the 128-row tiles
     // Measured per layer against the kernels it replaces (tools/conv_sweep.py, profiles/r03c_halo_sweep.txt): at 1024 frames per pass every deep
     // layer gains 12-18 % (14x14: 421 -> 502-513 TFLOP/s, 28x28: 405-420 -> 487-523, 56x56: 361-398 -> 431-483); at 128 frames the layers with
@@ -389,12 +387,10 @@ static int hs_launch(const ConvArgs& a, hipStream_t st, size_t lds) {
     if (const int rc = smirk_raise_dynamic_lds(a.stats ? fns : fn, 160 * 1024)) return rc;
     const int ntm = (a.M + HS_BM - 1) / HS_BM, ntn = a.N / HS_BN;
     if (g_smirk_prof_on) {
-        const double px = (double)a.d.B * a.d.H * a.d.W;
         char nm[64];
         if (X1) snprintf(nm, sizeof(nm), "conv_halo_x1_kernel<%d>[256x128,8w,halo,f16x1]", NPA);
         else snprintf(nm, sizeof(nm), "conv_halo_kernel<%d,%d>[256x128,8w,halo]", NPA, EB);
-        smirk_prof_next(nm, 2.0 * a.M * a.N * a.K,
-                        4.0 * (px * a.Cin + (double)a.M * a.N + (double)a.N * a.K + (a.residual ? (double)a.M * a.N : 0.0)));
+        conv_prof_next(nm, a);
     }
     if (a.stats) {
         if constexpr (X1) SMIRK_LAUNCH((conv_halo_x1_stats_kernel<NPA>), dim3(ntm * ntn), dim3(512), lds, st, a);

@@ -14,9 +14,7 @@
 // Bound: HBM (activation read 1.27x + write 1x) once the DMA is hidden; MFMA work is ~40 % of that time.
 #include <type_traits>
 
-#include "common.h"
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+#include "conv_common.h"
 
 #define PT 16                    // output patch edge
 #define PH (PT + 2)              // halo patch edge
@@ -673,11 +671,8 @@ int smirk_conv3x3_patch_launch(const SmirkConvDesc* d, const void* in0, const vo
     a.B = d->B; a.H = d->H; a.W = d->W; a.C0 = d->C0; a.C1 = d->C1; a.Cout = d->Cout; a.act = d->act;
     a.nchunk = (d->C0 + 31) / 32 + (d->C1 + 31) / 32;
     a.npatch = d->B * (d->H / PT) * (d->W / PT);
-    {
-        const long long px = (long long)d->B * d->H * d->W;
-        const bool pow2 = (d->C0 & (d->C0 - 1)) == 0 && (d->C1 & (d->C1 - 1)) == 0;
-        a.use_buf = (pow2 && px * d->C0 * 4 < (1ll << 31) && px * d->C1 * 4 < (1ll << 31)) ? 1 : 0;
-    }
+    const bool pow2 = (d->C0 & (d->C0 - 1)) == 0 && (d->C1 & (d->C1 - 1)) == 0;
+    a.use_buf = (pow2 && conv_inputs_fit32(*d)) ? 1 : 0;             // (weights reach LDS through plain pointers in either mode)
     if (g_smirk_prof_on) {
         const double px = (double)d->B * d->H * d->W, K = 9.0 * (d->C0 + d->C1);
         const double outb = fout ? px * fcout * 4.0 : px * d->Cout * 4.0;

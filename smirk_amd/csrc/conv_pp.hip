@@ -313,8 +313,7 @@ bool smirk_conv_pp_eligible(const ConvArgs& a) {
     if (d.Ho != d.H || d.Wo != d.W || d.W > 1023) return false;
     if (d.C0 % CV_BK || d.C1 % CV_BK || (d.C0 & (d.C0 - 1)) || (d.C1 & (d.C1 - 1))) return false;
     if (a.N % PP_BN || a.N < PP_BN) return false;
-    const long long b0 = (long long)d.B * d.H * d.W * d.C0 * 4, b1 = (long long)d.B * d.H * d.W * d.C1 * 4, bw = (long long)a.N * a.K * 4;
-    if (b0 >= (1ll << 31) || b1 >= (1ll << 31) || bw >= (1ll << 31)) return false;
+    if (!conv_operands_fit32(a)) return false;
     // Measured per layer at B = 128 (tools/conv_sweep.py --ab-pp, profiles/r02_conv_sweep_pp.txt): 14x14 layers 0.320-0.325 -> 0.277-0.279 ms
     // (K = 2304 / 4608: 72 / 144 chunks per tile amortise the exposed prologue + epilogue of the single workgroup per CU), 28x28 and 56x56
     // layers 1-9 % SLOWER (36-72 chunks per tile; the 128x128 kernel hides one workgroup's epilogue behind its co-resident twin's main
@@ -328,11 +327,7 @@ int smirk_conv_pp_launch(const ConvArgs& a, hipStream_t st) {
     // NL = 3 of a wave's 6 LDS-DMA instructions per chunk are issued in its load phase, 3 among the MFMAs.  0 / 2 / 6 measured the same within 1 % (0.279-0.281 ms on
     // the 14 x 14 layer, profiles/r02_conv_pp_dma_split.txt); the $SMIRK_PP_NL switch and those instantiations left the library in round 5.
     const int ntm = (a.M + PP_BM - 1) / PP_BM, ntn = a.N / PP_BN;
-    if (g_smirk_prof_on) {
-        const double px = (double)a.d.B * a.d.H * a.d.W;
-        smirk_prof_next("conv_pp_kernel<3>[256x128,8w,3stage]", 2.0 * a.M * a.N * a.K,
-                        4.0 * (px * a.Cin + (double)a.M * a.N + (double)a.N * a.K + (a.residual ? (double)a.M * a.N : 0.0)));
-    }
+    conv_prof_next("conv_pp_kernel<3>[256x128,8w,3stage]", a);
     SMIRK_LAUNCH(conv_pp_kernel<3>, dim3(ntm * ntn), dim3(512), PP_LDS_BYTES, st, a);
     return smirk_launch_status();
 }

@@ -288,8 +288,7 @@ bool smirk_conv3x3_ring64_eligible(const SmirkConvDesc* d, bool has_residual) {
     if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad_t != 1 || d->pad_l != 1 || d->pad_mode != SMIRK_PAD_ZERO) return false;
     if (d->out_mode != SMIRK_OUT_NHWC || d->Ho != d->H || d->Wo != d->W || d->H % RG_PT || d->W % RG_PT || d->H < 64 || has_residual) return false;
     if ((d->Cout != 64 && !(d->Cout == 32 && d->C0 + d->C1 >= 64)) || d->C0 < 32 || d->C0 % 32 || d->C1 % 32 || (d->C0 & (d->C0 - 1)) || (d->C1 & (d->C1 - 1))) return false;
-    const long long px = (long long)d->B * d->H * d->W;
-    return px * d->C0 * 4 < (1ll << 31) && px * d->C1 * 4 < (1ll << 31);
+    return conv_inputs_fit32(*d);                                     // (the weights, 9 (C0 + C1) x 64 at most, cannot reach the limit before an input does)
 }
 
 template <int TN, bool POOL, bool STATS = false>

@@ -609,9 +609,6 @@ extern "C" int smirk_vertices2landmarks(const float* verts, int B, int V, const 
     return smirk_launch_status();
 }
 
-extern "C" int smirk_conv_igemm_f32(const SmirkConvDesc* d, const float* in0, const float* in1, const float* w, const float* scale,
-                                    const float* shift, const float* residual, float* out, void* stream);
-
 static size_t bwd_off(size_t& cur, size_t bytes) { const size_t o = cur; cur += smirk_align_up(bytes, 256); return o; }
 
 extern "C" size_t smirk_flame_backward_workspace_bytes(const SmirkFlameModel* m, int B) {
