@@ -610,6 +610,48 @@ int smirk_loss_forward(const SmirkLossTerm* terms, int n_terms, float* out_terms
 int smirk_loss_backward(const SmirkLossTerm* terms, int n_terms, const float* grad_total, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Perceptual (VGG-16) term of the first path (smirk_trainer.py:104 `self.vgg_loss(reconstructed_img, img)`; src/losses/VGGPerceptualLoss.py:23-47):
+ * everything around the ten convolutions, which run on smirk_conv_igemm_f16x3 (shift = bias, ReLU) and, for the data gradients, on the same entry
+ * with the rotated weights of smirk_pack_conv_weights_split16; the pools are smirk_maxpool2x2_split16 / smirk_maxpool2x2_backward_split16.  The weights
+ * are frozen: no weight gradient exists.  Every entry launches on `stream`; no host synchronisation, no allocation, no copy, no atomics.
+ *
+ * prepare: x, y [B][3][H][W] fp32 NCHW in [-1, 1] -> out [2B][H][W][8] split16 (rows 0..B-1 from x, B..2B-1 from y, channels 3..7 zero) with
+ *   out_c = (0.5 v + 0.5 - mean[c]) / std[c] in fp32 (VGGPerceptualLoss.py:24-27); mean / std: device [3] (the module's buffers).  What is stored is
+ *   audited for the split-fp16 range in the NaN-catching form (the inputs come from outside the library).
+ * prepare_backward: d [B][H][W][8] split16 (gradient of the x rows of `out`) -> dx [B][3][H][W] fp32 = d_c / std[c] * 0.5 * scale.
+ *
+ * l1_partials: f [2 * half_elems] split16, the feature tensor [2B][M][C] of tap `tap` (half_elems = B * M * C): one float64 partial of
+ *   sum |fx - fy| (first half against second) per chunk of SMIRK_VGG_L1_CHUNK 8-channel groups of a half, stored at the tap's range of the workspace.
+ *   d is taken in fp32 from the decoded pairs (hi + lo * 2^-11 is exact in fp32), |d| summed in float64: per thread in group order, across the wave by a
+ *   fixed butterfly, across the four waves in wave order.  `half_elems` [n_taps] (host array, 1 <= n_taps <= SMIRK_VGG_TAPS) states every tap of the
+ *   call sequence: the chunk -> partial mapping depends on it alone, so two calls return the same bits.
+ * l1_finalise: one wave per tap adds the tap's partials (every lane a strided share in index order, then the same butterfly), term[k] = sum / half_elems[k]
+ *   -> out_terms [n_taps] fp32; out_total [1] = the sum of the UNROUNDED terms in float64, rounded once (VGGPerceptualLoss.py:38, 47).
+ *
+ * relu_tap_backward: one kernel, two modes, over the x rows only (elems = B * M * C values each of fx, d_in, dz; all split16):
+ *   fy == NULL (a layer that is not tapped): dz = d_in * [fx > 0]                                         (d_in required)
+ *   fy != NULL (a tapped layer):             dz = (d_in + g * coef * sign(fx - fy)) * [fx > 0]            (d_in NULL for the deepest tap: taken as 0)
+ *   with coef = scale / elems, g = the upstream gradient of the total read from the DEVICE pointer grad_total, sign(0) = 0.  dz is audited.
+ *   scale: the backward pass is linear, and 1 / elems lies deep in fp16's subnormal range, where a split16 pair resolves 2^-35 absolutely; the caller lifts the
+ *   injected term by a power of two S here and passes 1 / S to prepare_backward, both exact.
+ *
+ * Errors, all before the device is touched: NULL or not 16-byte aligned tensor / workspace pointers (mean, std, grad_total, outputs of finalise: NULL),
+ * B, H, W < 1, n_taps outside 1..SMIRK_VGG_TAPS, tap outside 0..n_taps-1, elems or an entry of half_elems below 8 or not a multiple of 8 (whole
+ * 8-channel groups), C < 8 or C % 8 != 0, scale not positive and finite, fy == NULL && d_in == NULL, fy != NULL && grad_total == NULL -> SMIRK_ERR_BAD_ARG; a tensor of 2 GiB and more (the limit of the
+ * convolution entries these tensors come from and go to) -> SMIRK_ERR_UNSUPPORTED; ws_bytes below smirk_vgg_l1_workspace_bytes -> SMIRK_ERR_WORKSPACE
+ * (the size query returns 0 for arguments the entries refuse).
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define SMIRK_VGG_TAPS 4
+#define SMIRK_VGG_L1_CHUNK 4096
+int smirk_vgg_prepare_split16(const float* x, const float* y, const float* mean, const float* std, void* out, int B, int H, int W, void* stream);
+int smirk_vgg_prepare_backward_split16(const void* d, const float* std, float* dx, int B, int H, int W, float scale, void* stream);
+size_t smirk_vgg_l1_workspace_bytes(const long long* half_elems, int n_taps);
+int smirk_vgg_l1_partials_split16(const void* f, int C, int tap, const long long* half_elems, int n_taps, void* ws, size_t ws_bytes, void* stream);
+int smirk_vgg_l1_finalise(const long long* half_elems, int n_taps, const void* ws, size_t ws_bytes, float* out_terms, float* out_total, void* stream);
+int smirk_vgg_relu_tap_backward_split16(const void* fx, const void* fy, const void* d_in, const float* grad_total, void* dz, long long elems, int C,
+                                        float scale, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Video loop pre/post-processing — replaces the cv2 / skimage calls of demo_video.py:107-214 so that a batch
  * of decoded frames stays in HBM from uint8 in to uint8 out.  uint8 images are HWC (cv2 layout), float images NCHW in [0,1].
  * ------------------------------------------------------------------------------------------------------------------ */

@@ -50,6 +50,7 @@ from .video import VideoPipeline  # noqa: F401  (demo_video.py's frame loop, bat
 from .augment import TemplateBank, augment_flame_params, load_templates  # noqa: F401  (smirk_trainer.py:192-248: the cycle path's augmented parameters)
 from .losses import FirstPathLoss, LossTerms, weighted_loss  # noqa: F401  (smirk_trainer.py:56-154: the first path's loss head; losses.cycle_loss: :304-313)
 from . import first_path, losses  # noqa: F401  (smirk_trainer.py:34-154 over the modules)
+from .vgg_loss import VGGPerceptualLoss  # noqa: E402,F401  (smirk_trainer.py:104: the first path's perceptual term; drop-in for src.losses.VGGPerceptualLoss)
 
 
 
@@ -62,4 +63,4 @@ def check_numerics():
 
 
 __all__ = ["FLAME", "Renderer", "SmirkEncoder", "SmirkGenerator", "SmirkHipError", "lib", "masking", "VideoPipeline", "check_numerics", "TemplateBank", "augment_flame_params",
-           "load_templates", "FirstPathLoss", "LossTerms", "weighted_loss", "losses", "first_path"]
+           "load_templates", "FirstPathLoss", "LossTerms", "weighted_loss", "losses", "first_path", "VGGPerceptualLoss"]

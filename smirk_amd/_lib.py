@@ -11,7 +11,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libsmirk_hip.so")
 LIB_PATH = os.environ.get("SMIRK_HIP_LIBRARY", LIB_PATH)      # tuning aid: A/B a differently-built libsmirk_hip.so in one gpurun
-ABI_VERSION = 13
+ABI_VERSION = 14
 PACK_DEPTHWISE, PACK_STEM, PACK_CONVT2X2 = -3, -27, -2          # SmirkPackJob.KH markers (include/smirk_hip.h SMIRK_PACK_*)
 SMIRK_OK, SMIRK_ERR_BAD_ARG, SMIRK_ERR_WORKSPACE, SMIRK_ERR_LAUNCH, SMIRK_ERR_UNSUPPORTED = 0, -1, -2, -3, -4      # include/smirk_hip.h
 
@@ -68,6 +68,7 @@ class SmirkProfileRecord(C.Structure):
 
 LOSS_MAX_TERMS, LOSS_CHUNK = 8, 4096                            # include/smirk_hip.h SMIRK_LOSS_MAX_TERMS, SMIRK_LOSS_CHUNK
 LOSS_SQUARE, LOSS_ABS_IMAGE = 0, 1                               # SmirkLossTerm.kind
+VGG_TAPS, VGG_L1_CHUNK = 4, 4096                                 # include/smirk_hip.h SMIRK_VGG_TAPS, SMIRK_VGG_L1_CHUNK (8-channel groups of a half per partial)
 
 
 class SmirkLossTerm(C.Structure):
@@ -188,6 +189,12 @@ _SIGS = {
     "smirk_loss_workspace_bytes": (_sz, [C.POINTER(SmirkLossTerm), _i]),
     "smirk_loss_forward": (_i, [C.POINTER(SmirkLossTerm), _i, _p, _p, _p, _sz, _p]),
     "smirk_loss_backward": (_i, [C.POINTER(SmirkLossTerm), _i, _p, _p, _sz, _p]),
+    "smirk_vgg_prepare_split16": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "smirk_vgg_prepare_backward_split16": (_i, [_p, _p, _p, _i, _i, _i, C.c_float, _p]),
+    "smirk_vgg_l1_workspace_bytes": (_sz, [C.POINTER(C.c_longlong), _i]),
+    "smirk_vgg_l1_partials_split16": (_i, [_p, _i, _i, C.POINTER(C.c_longlong), _i, _p, _sz, _p]),
+    "smirk_vgg_l1_finalise": (_i, [C.POINTER(C.c_longlong), _i, _p, _sz, _p, _p, _p]),
+    "smirk_vgg_relu_tap_backward_split16": (_i, [_p, _p, _p, _p, _p, C.c_longlong, _i, C.c_float, _p]),
 }
 EXPORTS = tuple(_SIGS)
 
