@@ -863,16 +863,15 @@ __global__ __launch_bounds__(256) void split16_to_f32_kernel(const float* __rest
         *(f32x4*)(out + i * 8 + 4) = *(f32x4*)(v + 4);
     }
 }
-static unsigned grid_for(size_t total, unsigned cap) { const size_t g = (total + 255) / 256; return (unsigned)(g > cap ? cap : (g ? g : 1)); }
 
 extern "C" int smirk_f32_to_split16(const float* in, void* out, size_t n_elems, void* stream) {
     if (!in || !out || n_elems % 8) return SMIRK_ERR_BAD_ARG;
-    SMIRK_LAUNCH(f32_to_split16_kernel, dim3(grid_for(n_elems / 8, 16384)), dim3(256), 0, (hipStream_t)stream, in, (float*)out, n_elems / 8);
+    SMIRK_LAUNCH(f32_to_split16_kernel, dim3(blocks_for(n_elems / 8, 16384)), dim3(256), 0, (hipStream_t)stream, in, (float*)out, n_elems / 8);
     return smirk_launch_status();
 }
 extern "C" int smirk_split16_to_f32(const void* in, float* out, size_t n_elems, void* stream) {
     if (!in || !out || n_elems % 8) return SMIRK_ERR_BAD_ARG;
-    SMIRK_LAUNCH(split16_to_f32_kernel, dim3(grid_for(n_elems / 8, 16384)), dim3(256), 0, (hipStream_t)stream, (const float*)in, out, n_elems / 8);
+    SMIRK_LAUNCH(split16_to_f32_kernel, dim3(blocks_for(n_elems / 8, 16384)), dim3(256), 0, (hipStream_t)stream, (const float*)in, out, n_elems / 8);
     return smirk_launch_status();
 }
 
@@ -896,7 +895,7 @@ __global__ __launch_bounds__(256) void split16_range_kernel(const float* __restr
 
 extern "C" int smirk_split16_range_check(const void* in, size_t n_elems, float limit, uint32_t* counts, void* stream) {
     if (!in || !counts || n_elems % 8) return SMIRK_ERR_BAD_ARG;
-    SMIRK_LAUNCH(split16_range_kernel, dim3(grid_for(n_elems / 8, 4096)), dim3(256), 0, (hipStream_t)stream, (const float*)in, n_elems / 8, limit, counts);
+    SMIRK_LAUNCH(split16_range_kernel, dim3(blocks_for(n_elems / 8, 4096)), dim3(256), 0, (hipStream_t)stream, (const float*)in, n_elems / 8, limit, counts);
     return smirk_launch_status();
 }
 
@@ -931,7 +930,7 @@ extern "C" int smirk_maxpool2x2_split16(const void* in, void* out, int B, int H,
     if (!in || !out || B <= 0 || H % 2 || W % 2 || C % 8 || C <= 0) return SMIRK_ERR_BAD_ARG;
     const size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 8);
     smirk_prof_next(nullptr, 0.0, 5.0 * total * 32);          // reads 4 groups, writes 1 (32 bytes per split16 group)
-    SMIRK_LAUNCH(maxpool2x2_split_kernel, dim3(grid_for(total, 16384)), dim3(256), 0, (hipStream_t)stream, (const float*)in,
+    SMIRK_LAUNCH(maxpool2x2_split_kernel, dim3(blocks_for(total, 16384)), dim3(256), 0, (hipStream_t)stream, (const float*)in,
                        (float*)out, B, H, W, C / 8);
     return smirk_launch_status();
 }
@@ -962,7 +961,7 @@ extern "C" int smirk_pack_generator_input_split16(const float* a, int Ca, const 
                                                   void* stream) {
     if (!a || !out || B <= 0 || Ca <= 0 || Cb < 0 || Ca + Cb > 8 || (Cb > 0 && !b)) return SMIRK_ERR_BAD_ARG;
     smirk_prof_next(nullptr, 0.0, (double)B * H * W * ((Ca + Cb) * 4 + 32));
-    SMIRK_LAUNCH(pack_split_kernel, dim3(grid_for((size_t)B * H * W, 16384)), dim3(256), 0, (hipStream_t)stream, a, Ca, b, Cb,
+    SMIRK_LAUNCH(pack_split_kernel, dim3(blocks_for((size_t)B * H * W, 16384)), dim3(256), 0, (hipStream_t)stream, a, Ca, b, Cb,
                        (float*)out, B, H * W);
     return smirk_launch_status();
 }
@@ -1002,7 +1001,7 @@ __global__ __launch_bounds__(256) void conv1x1_sigmoid_split_kernel(const float*
 extern "C" int smirk_conv1x1_sigmoid_nchw_split16(const void* in, const float* w, const float* bias, float* out, int B, int H,
                                                   int W, int C, int Cout, void* stream) {
     if (!in || !w || !out || B <= 0 || C % 8 || C <= 0 || Cout <= 0 || Cout > 4) return SMIRK_ERR_BAD_ARG;
-    SMIRK_LAUNCH(conv1x1_sigmoid_split_kernel, dim3(grid_for((size_t)B * H * W, 16384)), dim3(256),
+    SMIRK_LAUNCH(conv1x1_sigmoid_split_kernel, dim3(blocks_for((size_t)B * H * W, 16384)), dim3(256),
                        (size_t)(Cout * C + Cout) * 4, (hipStream_t)stream, (const float*)in, w, bias, out, B, H * W, C, Cout);
     return smirk_launch_status();
 }

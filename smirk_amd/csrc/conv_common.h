@@ -1,5 +1,6 @@
-// Shared pieces of the convolution kernels (conv.hip and the conv_*.hip units it dispatches to): argument block, GEMM-row -> pixel map, the split-fp16
-// conversions, the XOR-swizzled LDS operand image, the operand-size predicate of the buffer-addressed loads and the cross-unit launcher prototypes.
+// Shared pieces of the convolution kernels (conv.hip and the conv_*.hip units it dispatches to) and of the training units (wgrad.hip, train.hip,
+// train_encoder.hip): argument block, GEMM-row -> pixel map, the split-fp16 conversions and the 8-channel group access, the XOR-swizzled LDS operand image,
+// the operand-size predicate of the buffer-addressed loads, the grid of a grid-stride launch and the cross-unit launcher prototypes.
 // See conv.hip for the design notes.
 #pragma once
 #include "common.h"
@@ -67,6 +68,18 @@ __device__ __forceinline__ void split8(const float* v, half8& hi, half8& lo, RA&
     }
 }
 __device__ __forceinline__ float join1(_Float16 hi, _Float16 lo) { return (float)hi + (float)lo * (1.0f / 2048.0f); }
+// one 8-channel split16 group (hi halves, then lo halves) <-> 8 fp32 values: the access of every streaming kernel of the training units
+__device__ __forceinline__ void load_group(const float* p, float* v) {
+    const half8 hi = *(const half8*)p, lo = *(const half8*)(p + 4);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] = join1(hi[q], lo[q]);
+}
+__device__ __forceinline__ void store_group(float* p, const float* v) {
+    half8 hi, lo;
+    split8(v, hi, lo);
+    *(half8*)p = hi;
+    *(half8*)(p + 4) = lo;
+}
 
 
 // LDS operand image: [rows][32 dwords] (one 128-byte K chunk per row), written by global_load_lds_dwordx4 — 64 lanes x 16 B =
@@ -84,6 +97,11 @@ __device__ __forceinline__ int xcd_logical(int id, int nblk) {
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
+// grid of a grid-stride kernel with 256 threads per block: one thread per item, at most `cap` blocks
+static inline unsigned blocks_for(size_t items, unsigned cap) {
+    const size_t g = (items + 255) / 256;
+    return (unsigned)(g > cap ? cap : (g ? g : 1));
+}
 // Buffer-addressed operand DMA (`buffer_load_dwordx4 ... offen lds`) reaches a tensor through 32-bit byte offsets and a 32-bit num_records: the tensor must
 // end below 2 GiB.  `dwords` = its size in 4-byte elements (fp32, or split-fp16 pairs).
 #define CONV_BUF_LIMIT (1ll << 31)

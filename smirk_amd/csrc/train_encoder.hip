@@ -2,7 +2,7 @@
 // feature extractors the reference builds in smirk_encoder.py:7-12 are stem conv 3x3/s2 + depthwise-separable / inverted-residual blocks of
 // {pointwise 1x1, depthwise 3x3, BatchNorm, ReLU} + global average pool + Linear head (smirk_encoder.py:14-22, :48-56, :76-85).
 // Pointwise convolutions (forward, data gradient, weight gradient) and BatchNorm run on the kernels the generator's training path already has
-// (conv.hip / train.hip).  This file adds what is specific to the encoder:
+// (conv.hip / wgrad.hip / train.hip).  This file adds what is specific to the encoder:
 //   * depthwise 3x3 (stride 1 / TF-'SAME' stride 2) data gradient (+ optional skip gradient) and weight gradient,
 //   * the stem's weight gradient and data gradient (the image gradient the cycle path sends back into the generator, smirk_trainer.py:293-297),
 //   * global-average-pool + Linear backward.
@@ -14,21 +14,6 @@
 
 namespace {
 
-__device__ __forceinline__ void load_group(const float* p, float* v) {
-    const half8 hi = *(const half8*)p, lo = *(const half8*)(p + 4);
-#pragma unroll
-    for (int q = 0; q < 8; ++q) v[q] = join1(hi[q], lo[q]);
-}
-__device__ __forceinline__ void store_group(float* p, const float* v) {
-    half8 hi, lo;
-    split8(v, hi, lo);
-    *(half8*)p = hi;
-    *(half8*)(p + 4) = lo;
-}
-inline unsigned blocks_for(size_t items, unsigned cap) {
-    const size_t g = (items + 255) / 256;
-    return (unsigned)(g > cap ? cap : (g ? g : 1));
-}
 // TF 'SAME' leading pad for kernel 3 (timm Conv2dSame): total = max((ceil(n/s)-1)*s + 3 - n, 0); leading = total/2.  stride 1 => 1.
 __host__ __device__ inline int pad_lead(int n, int s) {
     if (s == 1) return 1;

@@ -1,5 +1,5 @@
 // Perceptual (VGG-16) term of the trainer's first path for MI355X (gfx950): everything AROUND the ten convolutions of src/losses/VGGPerceptualLoss.py:23-47
-// (smirk_trainer.py:104).  The convolutions, their data gradients and the pools are the existing entries (conv.hip, train.hip); this unit holds
+// (smirk_trainer.py:104).  The convolutions, their data gradients and the pools are the existing entries (conv.hip, wgrad.hip, train.hip); this unit holds
 //   vgg_prepare_kernel            x, y NCHW fp32 -> ONE split16 NHWC tensor [2B][H][W][8]: the affine map of :24-27 in fp32, NCHW -> NHWC, channel padding and the
 //                                 split in one pass; the range audit in its NaN-catching form (these values come from outside the library)
 //   vgg_prepare_backward_kernel   d [B][H][W][8] split16 -> dx [B][3][H][W] fp32 = d_c / std_c * 0.5 (autograd's own order of the two operations)

@@ -195,7 +195,7 @@ class SmirkGenerator(nn.Module):
         L.raise_if_range_tripped("smirk_amd.SmirkGenerator.forward")      # an overflow of the split-fp16 format in an EARLIER call is reported now (no sync)
         if self.training:
             # train mode (smirk_trainer.py:349-355 calls self.train() before every step): batch-statistics BatchNorm with running-stat updates and a
-            # real backward pass — one autograd.Function over the whole network (smirk_amd/generator_train.py, csrc/train.hip)
+            # real backward pass — one autograd.Function over the whole network (smirk_amd/generator_train.py, csrc/train.hip, csrc/wgrad.hip)
             if self.precision != "f16x3":
                 raise L.SmirkHipError("train mode runs in the split-fp16 ('f16x3') arithmetic mode")
             if self.in_channels > 8:

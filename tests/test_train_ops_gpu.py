@@ -1,4 +1,4 @@
-"""GPU parity of the individual TRAINING kernels (csrc/train.hip + the data-gradient use of the forward conv kernels), one op at a time,
+"""GPU parity of the individual TRAINING kernels (csrc/train.hip, csrc/wgrad.hip + the data-gradient use of the forward conv kernels), one op at a time,
 against float64 torch autograd of the op the reference's module graph contains (smirk_generator.py:88-119 `_block`, :121-178 ResnetBlock,
 :40-49 up-convs and head).
 

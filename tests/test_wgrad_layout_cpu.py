@@ -1,4 +1,4 @@
-"""Host-side model of the split-fp16 weight-gradient kernels' data movement (smirk_amd/csrc/train.hip: wgrad_f16_kernel, wgrad3x3_halo_f16_kernel).
+"""Host-side model of the split-fp16 weight-gradient kernels' data movement (smirk_amd/csrc/wgrad.hip: wgrad_f16_kernel, wgrad3x3_halo_f16_kernel).
 
 The kernels stage split16 operands into LDS with `slot(h, g, k)` and build their MFMA operands with gfx950's transpose read `ds_read_b64_tr_b16`.  This file
 restates (a) the slot function, (b) the transpose read as measured on the MI355X (tools/tr_probe.py, profiles/r02w_wgrad_f16_sweep.txt: lane 4r+q of a 16-lane

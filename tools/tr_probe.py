@@ -1,4 +1,4 @@
-"""Lane geometry of gfx950's LDS transpose read `ds_read_b64_tr_b16` (the weight-gradient kernels of train.hip build their MFMA operands with it).
+"""Lane geometry of gfx950's LDS transpose read `ds_read_b64_tr_b16` (the weight-gradient kernels of wgrad.hip build their MFMA operands with it).
 LDS holds halfs equal to their own index; lane l reads at byte address 8*l (a contiguous row-major [4][16] block per 16-lane group).  Expected (model "M1",
 what wgrad_f16_kernel assumes with trmap = 0): lane c of a group receives elements (c, 16 + c, 32 + c, 48 + c) of its group's 64-half block."""
 import ctypes, os, subprocess, torch
