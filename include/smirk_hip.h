@@ -333,6 +333,13 @@ int smirk_mbconv_supported(int Cin, int mid, int Cout, int stride);
 int smirk_mbconv_fused_split16(const void* x, const void* wexp, const float* s1, const float* b1, const float* wdw, const float* s2,
                                const float* b2, const void* wproj, const float* s3, const float* b3, int residual, void* out,
                                int B, int H, int W, int Cin, int mid, int Cout, int stride, void* stream);
+/* Stride-2 InvertedResidual block (no residual) with ONE WAVE per 4 x 8 output tile and no workgroup barrier in a tile's lifetime (csrc/mbconv_s2.hip): the
+ * arguments of smirk_mbconv_fused_split16 without `residual` and `stride`, and bit-identical results.  _supported: 1 for Cin 8 | 16 with Cout <= 32 and for
+ * Cin 24 | 32 with 40 <= Cout <= 64, mid <= 96 (all multiples of 8); any H, W >= 1.  s2 and b2 must be 16-byte aligned (SMIRK_ERR_BAD_ARG otherwise). */
+int smirk_mbconv_s2_supported(int Cin, int mid, int Cout);
+int smirk_mbconv_s2_split16(const void* x, const void* wexp, const float* s1, const float* b1, const float* wdw, const float* s2, const float* b2,
+                            const void* wproj, const float* s3, const float* b3, void* out, int B, int H, int W, int Cin, int mid, int Cout,
+                            void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Whole-network entries (SURVEY.md §8(b) proposal): ONE call enqueues every layer of a module's forward on `stream`, so a host in any

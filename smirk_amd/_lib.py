@@ -11,7 +11,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libsmirk_hip.so")
 LIB_PATH = os.environ.get("SMIRK_HIP_LIBRARY", LIB_PATH)      # tuning aid: A/B a differently-built libsmirk_hip.so in one gpurun
-ABI_VERSION = 14
+ABI_VERSION = 15
 PACK_DEPTHWISE, PACK_STEM, PACK_CONVT2X2 = -3, -27, -2          # SmirkPackJob.KH markers (include/smirk_hip.h SMIRK_PACK_*)
 SMIRK_OK, SMIRK_ERR_BAD_ARG, SMIRK_ERR_WORKSPACE, SMIRK_ERR_LAUNCH, SMIRK_ERR_UNSUPPORTED = 0, -1, -2, -3, -4      # include/smirk_hip.h
 
@@ -112,6 +112,8 @@ _SIGS = {
     "smirk_mbconv_lds_bytes": (_sz, [_i, _i, _i, _i]),
     "smirk_mbconv_supported": (_i, [_i, _i, _i, _i]),
     "smirk_mbconv_fused_split16": (_i, [_p] * 10 + [_i, _p] + [_i] * 7 + [_p]),
+    "smirk_mbconv_s2_supported": (_i, [_i, _i, _i]),
+    "smirk_mbconv_s2_split16": (_i, [_p] * 11 + [_i] * 6 + [_p]),
     "smirk_warp_affine_u8": (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _p, _p, _p]),
     "smirk_resize_linear_u8": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "smirk_f32_nchw_to_u8_grid": (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _p]),

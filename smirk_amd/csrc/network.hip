@@ -4,7 +4,7 @@
 //   smirk_backbone_forward    one sub-encoder of SmirkEncoder.forward: timm MobileNetV3-minimal features[-1] -> GAP -> Linear (+ clamps)
 //                             (src/smirk_encoder.py:34-45, :66-73, :95-110; backbone per SURVEY.md App. A)
 //
-// These are pure schedules over the per-layer entries of conv.hip / conv_patch.hip / encoder_ops.hip / mbconv.hip: which kernel serves a
+// These are pure schedules over the per-layer entries of conv.hip / conv_patch.hip / encoder_ops.hip / mbconv.hip / mbconv_s2.hip: which kernel serves a
 // layer is still decided by those dispatchers.  What moves here is the host-side walk (~60 launches for the generator, ~35-50 per
 // backbone): from Python + ctypes (~15 ms per 128-frame step, more than the GPU time of the step) to straight C++ (a few hundred
 // microseconds), and the activation memory from the framework's allocator to a caller-provided workspace that is laid out once:
@@ -442,6 +442,11 @@ extern "C" int smirk_backbone_forward(const SmirkBackboneWeights* w, const float
             void* o = p.rot.pick(x, nullptr);
             TRY(smirk_mbconv_image_split16(x, b.pw.w, b.pw.scale, b.pw.shift, (const float*)b.dw.w, b.dw.scale, b.dw.shift, b.pwl.w, b.pwl.scale, b.pwl.shift,
                                            b.skip ? 1 : 0, o, B, h, wd, b.cin, b.mid, b.cout, stream));
+            x = o;
+        } else if (split && !no_fuse && b.kind == 1 && b.stride == 2 && !b.skip && smirk_mbconv_s2_supported(b.cin, b.mid, b.cout)) {
+            void* o = p.rot.pick(x, nullptr);                       // stride-2 blocks down to 14 x 14: one wave per 4 x 8 output tile (mbconv_s2.hip), same bits as the kernel below
+            TRY(smirk_mbconv_s2_split16(x, b.pw.w, b.pw.scale, b.pw.shift, (const float*)b.dw.w, b.dw.scale, b.dw.shift, b.pwl.w, b.pwl.scale, b.pwl.shift,
+                                        o, B, h, wd, b.cin, b.mid, b.cout, stream));
             x = o;
         } else if (split && !no_fuse && (b.kind == 1 || fuse_ds) && smirk_mbconv_supported(b.cin, b.mid, b.cout, b.stride)) {
             void* o = p.rot.pick(x, nullptr);

@@ -260,6 +260,10 @@ class MobileNetV3Features(nn.Module):
             (we, s1, b1), (wd, s2, b2), (wp, s3, b3) = pk["pw"], pk["dw"], pk["pwl"]
         mid, cout, s = wd.shape[1], wp.shape[0], blk.stride
         out = torch.empty(B, (H + s - 1) // s, (W + s - 1) // s, cout, device=x.device)
+        if blk.kind == "ir" and s == 2 and not blk.skip and lib.smirk_mbconv_s2_supported(C, mid, cout):
+            # one wave per output tile (csrc/mbconv_s2.hip), as smirk_backbone_forward dispatches it
+            L.check(lib.smirk_mbconv_s2_split16(P(x), P(we), P(s1), P(b1), P(wd), P(s2), P(b2), P(wp), P(s3), P(b3), P(out), B, H, W, C, mid, cout, st))
+            return out
         L.check(lib.smirk_mbconv_fused_split16(P(x), N(we), N(s1), N(b1), P(wd), P(s2), P(b2), P(wp), P(s3), P(b3), int(bool(blk.skip)),
                                                P(out), B, H, W, C, mid, cout, s, st))
         return out
