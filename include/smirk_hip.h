@@ -403,6 +403,21 @@ size_t smirk_backbone_workspace_bytes(const SmirkBackboneWeights* w /*host struc
  * per sub-encoder, each on its own stream and workspace, to let their small launches interleave. */
 int smirk_backbone_forward(const SmirkBackboneWeights* w, const float* img, int B, int H, int W, float* out, void* feat_out,
                            void* ws, size_t ws_bytes, void* stream);
+/* Which kernel family smirk_backbone_forward takes for every block (csrc/network.hip backbone_plan; DESIGN.md 19 has the priority table).  HEAD_FUSED is block 0
+ * computed together with the stem in one launch (smirk_encoder_head_fused_split16); with the stem on its own block 0 has a family like any other block. */
+enum SmirkBackboneFamily {
+    SMIRK_BACKBONE_HEAD_FUSED = 0,  /* stem + first DepthwiseSeparable block: smirk_encoder_head_fused_split16                      */
+    SMIRK_BACKBONE_CONV1X1 = 1,     /* ConvBnAct 1x1: smirk_conv_igemm_*                                                            */
+    SMIRK_BACKBONE_MBCONV_IMAGE = 2,/* smirk_mbconv_image_split16: 14 x 14 halo tiles or whole images per workgroup                 */
+    SMIRK_BACKBONE_MBCONV_S2 = 3,   /* smirk_mbconv_s2_split16: stride 2, one wave per output tile                                  */
+    SMIRK_BACKBONE_MBCONV_TILE = 4, /* smirk_mbconv_fused_split16: 8 x 8 output tiles (the fallback of the two above)               */
+    SMIRK_BACKBONE_DS_UNFUSED = 5,  /* DepthwiseSeparable as depthwise + pointwise launches                                         */
+    SMIRK_BACKBONE_IR_UNFUSED = 6   /* InvertedResidual as pointwise + depthwise + pointwise launches                               */
+};
+/* The decisions of the forward call with the same arguments, without touching the device: family[i] (i < min(n_blocks, cap)) = SmirkBackboneFamily of block i.
+ * Reads the environment switches as the forward does.  Returns n_blocks, or SMIRK_ERR_BAD_ARG for what smirk_backbone_forward refuses for its weights / sizes
+ * (channels that do not chain from stem_cout through the blocks to feat_ch included; smirk_backbone_workspace_bytes returns 0 for those). */
+int smirk_backbone_plan(const SmirkBackboneWeights* w /*host struct*/, int B, int H, int W, int* family /*host*/, int cap);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Training-mode building blocks (BASELINE config 5, generator slice) — what autograd + nn.BatchNorm2d.train() compute inside the reference's

@@ -11,7 +11,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libsmirk_hip.so")
 LIB_PATH = os.environ.get("SMIRK_HIP_LIBRARY", LIB_PATH)      # tuning aid: A/B a differently-built libsmirk_hip.so in one gpurun
-ABI_VERSION = 15
+ABI_VERSION = 16
 PACK_DEPTHWISE, PACK_STEM, PACK_CONVT2X2 = -3, -27, -2          # SmirkPackJob.KH markers (include/smirk_hip.h SMIRK_PACK_*)
 SMIRK_OK, SMIRK_ERR_BAD_ARG, SMIRK_ERR_WORKSPACE, SMIRK_ERR_LAUNCH, SMIRK_ERR_UNSUPPORTED = 0, -1, -2, -3, -4      # include/smirk_hip.h
 
@@ -44,6 +44,7 @@ class SmirkConvLayer(C.Structure):
 
 GEN_MAX_RES, BACKBONE_MAX_BLOCKS = 16, 24
 PRECISION_F32, PRECISION_F16X3 = 0, 1
+BACKBONE_FAMILIES = ("HEAD_FUSED", "CONV1X1", "MBCONV_IMAGE", "MBCONV_S2", "MBCONV_TILE", "DS_UNFUSED", "IR_UNFUSED")   # enum SmirkBackboneFamily, by code
 
 
 class SmirkGeneratorWeights(C.Structure):
@@ -152,6 +153,7 @@ _SIGS = {
     "smirk_generator_forward": (_i, [C.POINTER(SmirkGeneratorWeights), _p, _i, _p, _i, _p, _i, _i, _i, C.POINTER(_p), _p, _sz, _p]),
     "smirk_backbone_workspace_bytes": (_sz, [C.POINTER(SmirkBackboneWeights), _i, _i, _i]),
     "smirk_backbone_forward": (_i, [C.POINTER(SmirkBackboneWeights), _p, _i, _i, _i, _p, _p, _p, _sz, _p]),
+    "smirk_backbone_plan": (_i, [C.POINTER(SmirkBackboneWeights), _i, _i, _i, C.POINTER(C.c_int), _i]),
     "smirk_train_reduce_workspace_bytes": (_sz, [_i]),
     "smirk_conv_stats_rows_max": (_sz, [C.POINTER(SmirkConvDesc)]),
     "smirk_conv_igemm_stats_split16": (_i, [C.POINTER(SmirkConvDesc), _p, _p, _p, _p, _p, C.POINTER(C.c_int), _i, _p]),

@@ -115,6 +115,14 @@ int smirk_device_cus();
 
 static inline size_t smirk_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// TF 'SAME' leading pad of a 3-tap kernel at stride s: total = max((ceil(n / s) - 1) * s + 3 - n, 0); leading = total / 2   (timm layers/padding.py)
+__host__ __device__ static inline int smirk_same_pad_lead(int n, int s) {
+    const int o = (n + s - 1) / s;
+    int t = (o - 1) * s + 3 - n;
+    if (t < 0) t = 0;
+    return t / 2;
+}
+
 static inline int smirk_launch_status() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? SMIRK_OK : SMIRK_ERR_LAUNCH;
@@ -151,6 +159,12 @@ void smirk_prof_begin(const char* name, hipStream_t st);
 void smirk_prof_end(hipStream_t st);
 // name (nullable: keep the stringified kernel), algorithmic flop and bytes of the NEXT launch made by this thread
 void smirk_prof_next(const char* name, double flop, double bytes);
+
+// the algorithmic work of one MBConv block for smirk_prof_next: expand 1x1 (InvertedResidual only), depthwise 3x3, project 1x1 over pin input / pout output
+// pixels; x is read once more where it is added back, the expanded tensors never reach memory
+static inline void smirk_prof_next_mbconv(const char* name, double pin, double pout, int Cin, int mid, int Cout, bool expand, bool residual) {
+    smirk_prof_next(name, 2.0 * (expand ? pin * Cin * mid : 0.0) + 2.0 * pout * mid * 9 + 2.0 * pout * mid * Cout, 4.0 * (pin * Cin * (residual ? 2 : 1) + pout * Cout));
+}
 
 struct SmirkLaunchScope {
     bool on;

@@ -23,14 +23,6 @@
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
-// TF 'SAME' leading pad for kernel 3: total = max((ceil(n/s)-1)*s + 3 - n, 0); leading = total/2   (timm layers/padding.py)
-__host__ __device__ static inline int eh_same_pad_lead(int n, int s) {
-    const int o = (n + s - 1) / s;
-    int t = (o - 1) * s + 3 - n;
-    if (t < 0) t = 0;
-    return t / 2;
-}
-
 struct EncHeadArgs {
     const float* img;                                   // [B][3][H][W] fp32
     const float *ws, *ss, *bs;                          // stem  [16][27] (k = (ky,kx,c)), folded BN scale / shift [16]
@@ -258,8 +250,8 @@ extern "C" int smirk_encoder_head_fused_split16(const float* img, const float* s
     a.sp = pw_scale; a.bp = pw_shift; a.out = (char*)out; a.B = B; a.H = H; a.W = W; a.residual = residual;
     a.Hs = (H + 1) / 2; a.Ws = (W + 1) / 2;
     a.Ho = (a.Hs + stride - 1) / stride; a.Wo = (a.Ws + stride - 1) / stride;
-    a.pts = eh_same_pad_lead(H, 2); a.pls = eh_same_pad_lead(W, 2);
-    a.ptd = stride == 1 ? 1 : eh_same_pad_lead(a.Hs, 2); a.pld = stride == 1 ? 1 : eh_same_pad_lead(a.Ws, 2);
+    a.pts = smirk_same_pad_lead(H, 2); a.pls = smirk_same_pad_lead(W, 2);
+    a.ptd = stride == 1 ? 1 : smirk_same_pad_lead(a.Hs, 2); a.pld = stride == 1 ? 1 : smirk_same_pad_lead(a.Ws, 2);
     const int TO = stride == 1 ? 16 : 8;
     a.tiles_x = (a.Wo + TO - 1) / TO; a.tiles_y = (a.Ho + TO - 1) / TO;
     const size_t nblk = (size_t)B * a.tiles_x * a.tiles_y;

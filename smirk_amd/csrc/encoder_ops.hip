@@ -18,14 +18,6 @@ __device__ __forceinline__ void enc_split8(const float* v, half8& hi, half8& lo)
 }
 __device__ __forceinline__ float enc_join(_Float16 hi, _Float16 lo) { return (float)hi + (float)lo * (1.0f / 2048.0f); }
 
-// TF 'SAME' leading pad for kernel 3: total = max((ceil(n/s)-1)*s + 3 - n, 0); leading = total/2
-__host__ __device__ static inline int same_pad_lead(int n, int s) {
-    const int o = (n + s - 1) / s;
-    int t = (o - 1) * s + 3 - n;
-    if (t < 0) t = 0;
-    return t / 2;
-}
-
 __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict__ img, const float* __restrict__ w,
                                                         const float* __restrict__ scale, const float* __restrict__ shift,
                                                         float* __restrict__ out, int B, int H, int W, int Cout, int split) {
@@ -36,7 +28,7 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict_
     for (int i = threadIdx.x; i < Cout; i += blockDim.x) { sw[27 * Cout + i] = raw ? 1.f : scale[i]; sw[28 * Cout + i] = raw ? 0.f : shift[i]; }
     __syncthreads();
     const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
-    const int pt = same_pad_lead(H, 2), pl = same_pad_lead(W, 2);
+    const int pt = smirk_same_pad_lead(H, 2), pl = smirk_same_pad_lead(W, 2);
     const size_t total = (size_t)B * Ho * Wo, HW = (size_t)H * W;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int ox = (int)(i % Wo), oy = (int)((i / Wo) % Ho);
@@ -102,7 +94,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_kernel(const f32x4* __restrict_
                                                         f32x4* __restrict__ out, int B, int H, int W, int C4, int stride,
                                                         int relu) {
     const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
-    const int pt = stride == 1 ? 1 : same_pad_lead(H, stride), pl = stride == 1 ? 1 : same_pad_lead(W, stride);
+    const int pt = stride == 1 ? 1 : smirk_same_pad_lead(H, stride), pl = stride == 1 ? 1 : smirk_same_pad_lead(W, stride);
     const size_t total = (size_t)B * Ho * Wo * C4;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int c = (int)(i % C4);
@@ -141,7 +133,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_split_kernel(const float* __res
                                                               float* __restrict__ out, int B, int H, int W, int G, int stride,
                                                               int relu) {
     const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
-    const int pt = stride == 1 ? 1 : same_pad_lead(H, stride), pl = stride == 1 ? 1 : same_pad_lead(W, stride);
+    const int pt = stride == 1 ? 1 : smirk_same_pad_lead(H, stride), pl = stride == 1 ? 1 : smirk_same_pad_lead(W, stride);
     const int C = G * 8;
     // a workgroup walks output ROWS (image, oy): row decomposition is scalar work, a lane needs ONE 32-bit division (e / G) per item.  The flat 64-bit
     // index this replaces cost three 64-bit divisions per item — ~45 % of the kernel's instructions, and the kernel is VALU-bound (2.2 TB/s measured)

@@ -343,13 +343,6 @@ __global__ __launch_bounds__(256, 3) void mbconv_fused_kernel(MBArgs a) {
     rng.commit();
 }
 
-static int mb_same_pad_lead(int n, int s) {
-    const int o = (n + s - 1) / s;
-    int t = (o - 1) * s + 3 - n;
-    if (t < 0) t = 0;
-    return t / 2;
-}
-
 extern "C" size_t smirk_mbconv_lds_bytes(int Cin, int mid, int Cout, int stride) {
     const int cinp = (Cin + 15) / 16 * 16, coutp = (Cout + 31) / 32 * 32, midp = (mid + 31) / 32 * 32;
     const int NH = stride == 1 ? 100 : 153, MH = (NH + 31) / 32 * 32, MO = stride == 1 ? 64 : 32;
@@ -366,12 +359,12 @@ extern "C" int smirk_mbconv_supported(int Cin, int mid, int Cout, int stride) {
 }
 
 template <int S, bool EXP>
-static void mb_launch(const MBArgs& a, dim3 grid, size_t lds, hipStream_t st, double flop, double bytes) {
+static void mb_launch(const MBArgs& a, dim3 grid, size_t lds, hipStream_t st) {
     const int ks = a.cinp / 16;
     if (g_smirk_prof_on) {
         char nm[64];
         snprintf(nm, sizeof(nm), "mbconv_fused_kernel<%d,%s,%d>", S, EXP ? "true" : "false", ks);
-        smirk_prof_next(nm, flop, bytes);
+        smirk_prof_next_mbconv(nm, (double)a.B * a.H * a.W, (double)a.B * a.Ho * a.Wo, a.Cin, a.mid, a.Cout, EXP, a.residual != 0);
     }
     if (ks == 1) SMIRK_LAUNCH((mbconv_fused_kernel<S, EXP, 1>), grid, dim3(256), lds, st, a);
     else if (ks == 2) SMIRK_LAUNCH((mbconv_fused_kernel<S, EXP, 2>), grid, dim3(256), lds, st, a);
@@ -392,7 +385,7 @@ extern "C" int smirk_mbconv_fused_split16(const void* x, const void* wexp, const
     a.wproj = (const char*)wproj; a.s3 = s3; a.b3 = b3; a.out = (char*)out;
     a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.mid = mid; a.Cout = Cout; a.residual = residual;
     a.Ho = (H + stride - 1) / stride; a.Wo = (W + stride - 1) / stride;
-    a.pt = stride == 1 ? 1 : mb_same_pad_lead(H, stride); a.pl = stride == 1 ? 1 : mb_same_pad_lead(W, stride);
+    a.pt = stride == 1 ? 1 : smirk_same_pad_lead(H, stride); a.pl = stride == 1 ? 1 : smirk_same_pad_lead(W, stride);
     a.cinp = (Cin + 15) / 16 * 16; a.coutp = (Cout + 31) / 32 * 32;
     const int THO = stride == 1 ? 8 : 4, NH = stride == 1 ? 100 : 153, MO = stride == 1 ? 64 : 32;
     a.tiles_x = (a.Wo + 7) / 8; a.tiles_y = (a.Ho + THO - 1) / THO;
@@ -401,10 +394,7 @@ extern "C" int smirk_mbconv_fused_split16(const void* x, const void* wexp, const
     const size_t lds = smirk_mbconv_lds_bytes(Cin, mid, Cout, stride);
     const dim3 grid((unsigned)((size_t)B * a.tiles_x * a.tiles_y));
     hipStream_t st = (hipStream_t)stream;
-    const double pin = (double)B * H * W, pout = (double)B * a.Ho * a.Wo;
-    const double flop = 2.0 * (wexp ? pin * Cin * mid : 0.0) + 2.0 * pout * mid * 9 + 2.0 * pout * mid * Cout;
-    const double bytes = 4.0 * (pin * Cin * (residual ? 2 : 1) + pout * Cout);
-    if (stride == 1) { if (wexp) mb_launch<1, true>(a, grid, lds, st, flop, bytes); else mb_launch<1, false>(a, grid, lds, st, flop, bytes); }
-    else { if (wexp) mb_launch<2, true>(a, grid, lds, st, flop, bytes); else mb_launch<2, false>(a, grid, lds, st, flop, bytes); }
+    if (stride == 1) { if (wexp) mb_launch<1, true>(a, grid, lds, st); else mb_launch<1, false>(a, grid, lds, st); }
+    else { if (wexp) mb_launch<2, true>(a, grid, lds, st); else mb_launch<2, false>(a, grid, lds, st); }
     return smirk_launch_status();
 }

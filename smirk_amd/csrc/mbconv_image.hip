@@ -417,13 +417,14 @@ extern "C" int smirk_mbconv_image_supported(int H, int W, int Cin, int mid, int 
 }
 
 template <int KS, int NT, bool TILE = false, bool PADK = false>
-static int mbi_launch(const MBIArgs& a, unsigned grid, size_t lds, hipStream_t st, double flop, double bytes) {
+static int mbi_launch(const MBIArgs& a, unsigned grid, size_t lds, hipStream_t st) {
     if (const int rc = smirk_raise_dynamic_lds((const void*)mbconv_image_kernel<KS, NT, TILE, PADK>, 160 * 1024)) return rc;
     if (g_smirk_prof_on) {
         char nm[64];
         if (TILE || PADK) snprintf(nm, sizeof(nm), "mbconv_image_kernel<%d,%d,%s,%s>", KS, NT, TILE ? "true" : "false", PADK ? "true" : "false");
         else snprintf(nm, sizeof(nm), "mbconv_image_kernel<%d,%d>", KS, NT);
-        smirk_prof_next(nm, flop, bytes);
+        const double px = (double)a.B * a.H * a.W;
+        smirk_prof_next_mbconv(nm, px, px, a.Cin, a.mid, a.Cout, true, a.residual != 0);
     }
     SMIRK_LAUNCH((mbconv_image_kernel<KS, NT, TILE, PADK>), dim3(grid), dim3(512), lds, st, a);
     return smirk_launch_status();
@@ -443,15 +444,12 @@ extern "C" int smirk_mbconv_image_split16(const void* x, const void* wexp, const
     a.tile = p.tile; a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y; a.gpitch = p.gpitch; a.rowsE = p.rowsE; a.nbE = p.nbE; a.off_gmapE = p.off_gmapE;
     const unsigned grid = p.tile ? (unsigned)B * p.tiles_x * p.tiles_y : (unsigned)((B + p.ipw - 1) / p.ipw);
     hipStream_t st = (hipStream_t)stream;
-    const double px = (double)B * H * W;
-    const double flop = 2.0 * px * ((double)Cin * mid + 9.0 * mid + (double)mid * Cout);
-    const double bytes = 4.0 * px * (Cin * (residual ? 2 : 1) + Cout);
     const int ks = (Cin + 15) / 16, nt = (Cout + 31) / 32;
-#define MBI_CASE(K, N) if (ks == K && nt == N) return mbi_launch<K, N>(a, grid, p.lds, st, flop, bytes)
+#define MBI_CASE(K, N) if (ks == K && nt == N) return mbi_launch<K, N>(a, grid, p.lds, st)
     MBI_CASE(5, 3); MBI_CASE(5, 4); MBI_CASE(6, 3); MBI_CASE(7, 4);          // mbi_has_variant lists the same pairs
     MBI_CASE(4, 2); MBI_CASE(4, 3); MBI_CASE(5, 2); MBI_CASE(6, 4); MBI_CASE(7, 3);
-    if (ks == 2 && nt == 1) return p.tile ? mbi_launch<2, 1, true, true>(a, grid, p.lds, st, flop, bytes) : mbi_launch<2, 1, false, true>(a, grid, p.lds, st, flop, bytes);
-    if (ks == 3 && nt == 2) return p.tile ? mbi_launch<3, 2, true, true>(a, grid, p.lds, st, flop, bytes) : mbi_launch<3, 2, false, true>(a, grid, p.lds, st, flop, bytes);
+    if (ks == 2 && nt == 1) return p.tile ? mbi_launch<2, 1, true, true>(a, grid, p.lds, st) : mbi_launch<2, 1, false, true>(a, grid, p.lds, st);
+    if (ks == 3 && nt == 2) return p.tile ? mbi_launch<3, 2, true, true>(a, grid, p.lds, st) : mbi_launch<3, 2, false, true>(a, grid, p.lds, st);
 #undef MBI_CASE
     return SMIRK_ERR_UNSUPPORTED;
 }

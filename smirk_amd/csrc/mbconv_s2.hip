@@ -319,13 +319,6 @@ __global__ __launch_bounds__(256, 2) void mbconv_s2_wave_kernel(MBS2Args a) {
     rng.commit();
 }
 
-static int s2w_same_pad_lead(int n) {
-    const int o = (n + 1) / 2;
-    int t = (o - 1) * 2 + 3 - n;
-    if (t < 0) t = 0;
-    return t / 2;
-}
-
 /* 1 if smirk_mbconv_s2_split16 serves this stride-2 InvertedResidual block: (ceil(Cin / 16), ceil(Cout / 32)) = (1, 1) | (2, 2), mid <= 96 */
 extern "C" int smirk_mbconv_s2_supported(int Cin, int mid, int Cout) {
     if (Cin <= 0 || mid <= 0 || Cout <= 0 || Cin % 8 || mid % 8 || Cout % 8 || mid > S2W_MAX_MID) return 0;
@@ -334,12 +327,12 @@ extern "C" int smirk_mbconv_s2_supported(int Cin, int mid, int Cout) {
 }
 
 template <int KS, int NT>
-static int s2w_launch(const MBS2Args& a, unsigned grid, size_t lds, hipStream_t st, double flop, double bytes) {
+static int s2w_launch(const MBS2Args& a, unsigned grid, size_t lds, hipStream_t st) {
     if (const int rc = smirk_raise_dynamic_lds((const void*)mbconv_s2_wave_kernel<KS, NT>, 80 * 1024)) return rc;
     if (g_smirk_prof_on) {
         char nm[64];
         snprintf(nm, sizeof(nm), "mbconv_s2_wave_kernel<%d,%d>", KS, NT);
-        smirk_prof_next(nm, flop, bytes);
+        smirk_prof_next_mbconv(nm, (double)a.B * a.H * a.W, (double)a.B * a.Ho * a.Wo, a.Cin, a.mid, a.Cout, true, false);
     }
     SMIRK_LAUNCH((mbconv_s2_wave_kernel<KS, NT>), dim3(grid), dim3(256), lds, st, a);
     return smirk_launch_status();
@@ -356,17 +349,14 @@ extern "C" int smirk_mbconv_s2_split16(const void* x, const void* wexp, const fl
     a.wproj = (const char*)wproj; a.s3 = s3; a.b3 = b3; a.out = (char*)out;
     a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.mid = mid; a.Cout = Cout;
     a.Ho = (H + 1) / 2; a.Wo = (W + 1) / 2;
-    a.pt = s2w_same_pad_lead(H); a.pl = s2w_same_pad_lead(W);
+    a.pt = smirk_same_pad_lead(H, 2); a.pl = smirk_same_pad_lead(W, 2);
     a.tiles_x = (a.Wo + 7) / 8; a.tiles_y = (a.Ho + 3) / 4;
     const size_t ntiles = (size_t)B * a.tiles_x * a.tiles_y;
     if (ntiles > 0x7fffffffu / 4 || (size_t)H * W * Cin * 4 > 0x7fffffffu) return SMIRK_ERR_UNSUPPORTED;   // 32-bit tile ids and in-image byte offsets
     a.ntiles = (int)ntiles;
     const size_t lds = (size_t)4 * S2W_EB + smirk_align_up((size_t)9 * mid * 4, 16);
     const unsigned grid = (unsigned)((ntiles + 3) / 4);
-    const double pin = (double)B * H * W, pout = (double)B * a.Ho * a.Wo;
-    const double flop = 2.0 * pin * Cin * mid + 2.0 * pout * mid * 9 + 2.0 * pout * mid * Cout;
-    const double bytes = 4.0 * (pin * Cin + pout * Cout);
     const int ks = (Cin + 15) / 16;
-    if (ks == 1) return s2w_launch<1, 1>(a, grid, lds, (hipStream_t)stream, flop, bytes);
-    return s2w_launch<2, 2>(a, grid, lds, (hipStream_t)stream, flop, bytes);
+    if (ks == 1) return s2w_launch<1, 1>(a, grid, lds, (hipStream_t)stream);
+    return s2w_launch<2, 2>(a, grid, lds, (hipStream_t)stream);
 }

@@ -4,8 +4,10 @@
 //   smirk_backbone_forward    one sub-encoder of SmirkEncoder.forward: timm MobileNetV3-minimal features[-1] -> GAP -> Linear (+ clamps)
 //                             (src/smirk_encoder.py:34-45, :66-73, :95-110; backbone per SURVEY.md App. A)
 //
-// These are pure schedules over the per-layer entries of conv.hip / conv_patch.hip / encoder_ops.hip / mbconv.hip / mbconv_s2.hip: which kernel serves a
-// layer is still decided by those dispatchers.  What moves here is the host-side walk (~60 launches for the generator, ~35-50 per
+// These are pure schedules over the per-layer entries of conv.hip / conv_patch.hip / encoder_ops.hip / encoder_head.hip / mbconv.hip / mbconv_image.hip /
+// mbconv_s2.hip: which kernel serves a convolution is still decided by those dispatchers.  Which ENTRY serves a backbone block is decided here, once, by
+// backbone_plan (one priority table, backbone_block_family); smirk_backbone_forward is a switch over that plan, smirk_backbone_workspace_bytes returns its bytes and
+// smirk_backbone_plan reports its families without touching the device.  What moves here is the host-side walk (~60 launches for the generator, ~35-50 per
 // backbone): from Python + ctypes (~15 ms per 128-frame step, more than the GPU time of the step) to straight C++ (a few hundred
 // microseconds), and the activation memory from the framework's allocator to a caller-provided workspace that is laid out once:
 //   * U-Net skip tensors e1..e4 have fixed slots,
@@ -353,35 +355,73 @@ bool backbone_args_ok(const SmirkBackboneWeights* w, int B, int H, int W) {
     return w->stem.w && w->stem.scale && w->stem.shift && w->stem_cout > 0;
 }
 
-// largest activation (in elements) any layer of the backbone reads or writes, walking the block list
-size_t backbone_max_elems(const SmirkBackboneWeights* w, int B, int H, int W) {
-    int h = (H + 1) / 2, wd = (W + 1) / 2;
-    size_t m = (size_t)B * h * wd * w->stem_cout;
+// The backbone's A/B switches (switches.h) as values: the entries read them once per call, so a test may set and unset them between calls.
+struct BackboneSwitches {
+    bool no_image, no_tile, no_fused, no_head;
+};
+
+BackboneSwitches backbone_switches() {
+    return {smirk_switch(SMIRK_SW_DISABLE_MBCONV_IMAGE) != 0, smirk_switch(SMIRK_SW_DISABLE_MBCONV_TILE) != 0, smirk_switch(SMIRK_SW_DISABLE_MBCONV_FUSED) != 0,
+            smirk_switch(SMIRK_SW_DISABLE_ENCODER_HEAD_FUSED) != 0};
+}
+
+// Which kernel family serves one block on an h x w input: the first row of this table whose condition holds (DESIGN.md 19 lists what every block of the two
+// backbones takes).  Rows 2-4 are for InvertedResidual blocks in the split-fp16 precision, unless $SMIRK_DISABLE_MBCONV_FUSED; each `*_supported` is the kernel's own
+// statement of what it serves and is not restated here.
+//   1  CONV1X1        ConvBnAct 1x1: one implicit-GEMM launch
+//   2  MBCONV_IMAGE   smirk_mbconv_image_supported (stride 1: 14 x 14 halo tiles or whole images per workgroup), unless $SMIRK_DISABLE_MBCONV_IMAGE, and unless
+//                     $SMIRK_DISABLE_MBCONV_TILE keeps a block that row 4 also serves on the 8 x 8-tile kernel
+//   3  MBCONV_S2      stride 2, no residual, smirk_mbconv_s2_supported: one wave per output tile
+//   4  MBCONV_TILE    smirk_mbconv_supported: 8 x 8 output tiles.  The FALLBACK of rows 2 and 3 — feature maps of more than 224 pixels with a side that is no multiple of 14, and the
+//                     IMAGE / TILE switches; at 224 x 224 no block of either backbone reaches it by default
+//   5  DS_UNFUSED     DepthwiseSeparable: depthwise, pointwise.  Never fused: it has no expanded tensor to keep on chip (202 vs 200 us at stride 1, 97 vs 66 at
+//      IR_UNFUSED     stride 2).  InvertedResidual: pointwise, depthwise, pointwise
+int backbone_block_family(const SmirkMbBlock& b, int h, int w, bool split, const BackboneSwitches& sw) {
+    if (b.kind == 2) return SMIRK_BACKBONE_CONV1X1;
+    if (b.kind == 1 && split && !sw.no_fused) {
+        const bool tile = smirk_mbconv_supported(b.cin, b.mid, b.cout, b.stride);
+        if (!sw.no_image && !(sw.no_tile && tile) && smirk_mbconv_image_supported(h, w, b.cin, b.mid, b.cout, b.stride)) return SMIRK_BACKBONE_MBCONV_IMAGE;
+        if (b.stride == 2 && !b.skip && smirk_mbconv_s2_supported(b.cin, b.mid, b.cout)) return SMIRK_BACKBONE_MBCONV_S2;
+        if (tile) return SMIRK_BACKBONE_MBCONV_TILE;
+    }
+    return b.kind == 0 ? SMIRK_BACKBONE_DS_UNFUSED : SMIRK_BACKBONE_IR_UNFUSED;
+}
+
+// Everything smirk_backbone_forward decides before it launches: a pure function of the weights' SHAPE fields, the batch, the image size and the switch values (no
+// pointer target, no environment, no device).  The workspace is three rotating slots sized for the largest activation any schedule of these blocks reads or writes —
+// the unfused temporaries included, because a switch may turn fusion off on the next call with the same workspace — and the pooled vectors of the head.
+struct BackbonePlan {
+    bool ok;                                            // false: the channels do not chain (stem_cout -> blocks -> feat_ch)
+    struct Block { int family, h, w, ho, wo; } blk[SMIRK_BACKBONE_MAX_BLOCKS];    // blk[0].family == SMIRK_BACKBONE_HEAD_FUSED: stem + block 0 in one launch
+    size_t slot_off[3], pooled_off, total;
+};
+
+BackbonePlan backbone_plan(const SmirkBackboneWeights* w, int B, int H, int W, const BackboneSwitches& sw) {
+    BackbonePlan p;
+    p.ok = false;
+    const bool split = w->precision == SMIRK_PRECISION_F16X3;
+    int h = (H + 1) / 2, wd = (W + 1) / 2, c = w->stem_cout;
+    size_t m = (size_t)B * h * wd * c;                   // largest activation, in elements
     for (int i = 0; i < w->n_blocks; ++i) {
         const SmirkMbBlock& b = w->blocks[i];
+        if (b.cin != c || b.stride < 1) return p;
         const int ho = (h + b.stride - 1) / b.stride, wo = (wd + b.stride - 1) / b.stride;
         const size_t in_mid = (size_t)B * h * wd * b.mid, out_mid = (size_t)B * ho * wo * b.mid, out = (size_t)B * ho * wo * b.cout;
         if (b.kind == 1 && in_mid > m) m = in_mid;
         if (b.kind != 2 && out_mid > m) m = out_mid;
         if (out > m) m = out;
-        h = ho; wd = wo;
+        p.blk[i] = {backbone_block_family(b, h, wd, split, sw), h, wd, ho, wo};
+        h = ho; wd = wo; c = b.cout;
     }
-    return m;
-}
-
-struct BackbonePlan {
-    Rot rot;
-    float* pooled;
-    size_t total;
-};
-
-BackbonePlan plan_backbone(const SmirkBackboneWeights* w, int B, int H, int W, void* ws) {
-    Arena a{(char*)ws, 0};
-    BackbonePlan p;
-    const size_t big = backbone_max_elems(w, B, H, W) * 4;
-    for (int i = 0; i < 3; ++i) p.rot.slot[i] = a.take(big);
-    p.pooled = (float*)a.take((size_t)B * w->feat_ch * 4);
-    p.total = smirk_align_up(a.off, 256);
+    if (c != w->feat_ch) return p;
+    p.ok = true;
+    const SmirkMbBlock& b0 = w->blocks[0];
+    if (split && !sw.no_head && smirk_encoder_head_supported(w->stem_cout, b0.kind, b0.cin, b0.mid, b0.cout, b0.stride, b0.skip))
+        p.blk[0].family = SMIRK_BACKBONE_HEAD_FUSED;    // encoder_head.hip: the 16-channel 112 x 112 tensors between stem and block 0 never reach HBM
+    size_t off = 0;
+    for (int i = 0; i < 3; ++i) { p.slot_off[i] = smirk_align_up(off, 256); off = p.slot_off[i] + m * 4; }
+    p.pooled_off = smirk_align_up(off, 256);
+    p.total = smirk_align_up(p.pooled_off + (size_t)B * w->feat_ch * 4, 256);
     return p;
 }
 
@@ -389,36 +429,28 @@ BackbonePlan plan_backbone(const SmirkBackboneWeights* w, int B, int H, int W, v
 
 extern "C" size_t smirk_backbone_workspace_bytes(const SmirkBackboneWeights* w, int B, int H, int W) {
     if (!backbone_args_ok(w, B, H, W)) return 0;
-    return plan_backbone(w, B, H, W, nullptr).total;
+    const BackbonePlan p = backbone_plan(w, B, H, W, BackboneSwitches{});          // (the layout does not depend on the switches)
+    return p.ok ? p.total : 0;
+}
+
+extern "C" int smirk_backbone_plan(const SmirkBackboneWeights* w, int B, int H, int W, int* family, int cap) {
+    if (!backbone_args_ok(w, B, H, W) || cap < 0 || (cap > 0 && !family)) return SMIRK_ERR_BAD_ARG;
+    const BackbonePlan p = backbone_plan(w, B, H, W, backbone_switches());
+    if (!p.ok) return SMIRK_ERR_BAD_ARG;
+    for (int i = 0; i < w->n_blocks && i < cap; ++i) family[i] = p.blk[i].family;
+    return w->n_blocks;
 }
 
 extern "C" int smirk_backbone_forward(const SmirkBackboneWeights* w, const float* img, int B, int H, int W, float* out, void* feat_out,
                                       void* ws, size_t ws_bytes, void* stream) {
     if (!backbone_args_ok(w, B, H, W) || !img || !ws || (w->n_out > 0 && !out) || (w->n_out == 0 && !feat_out)) return SMIRK_ERR_BAD_ARG;
-    const BackbonePlan p = plan_backbone(w, B, H, W, ws);
+    const BackbonePlan p = backbone_plan(w, B, H, W, backbone_switches());
+    if (!p.ok) return SMIRK_ERR_BAD_ARG;
     if (ws_bytes < p.total) return SMIRK_ERR_WORKSPACE;
     const bool split = w->precision == SMIRK_PRECISION_F16X3;
-    const bool no_image = smirk_switch(SMIRK_SW_DISABLE_MBCONV_IMAGE);                                                         // A/B switches (switches.h)
-    const bool no_tile = smirk_switch(SMIRK_SW_DISABLE_MBCONV_TILE);
-    const bool no_fuse = smirk_switch(SMIRK_SW_DISABLE_MBCONV_FUSED);
-    const bool fuse_ds = false;       // DepthwiseSeparable blocks stay unfused (no expanded tensor to save: 202 vs 200 us at stride 1, 97 vs 66 at stride 2)
-    int h = (H + 1) / 2, wd = (W + 1) / 2;
-    void* x = p.rot.slot[0];
-    // stem + first DepthwiseSeparable block in one launch (encoder_head.hip): the 16-channel 112 x 112 tensors between them never reach HBM
-    int first_block = 0;
-    {
-        const SmirkMbBlock& b0 = w->blocks[0];
-        const bool no_head = smirk_switch(SMIRK_SW_DISABLE_ENCODER_HEAD_FUSED);
-        if (split && !no_head && smirk_encoder_head_supported(w->stem_cout, b0.kind, b0.cin, b0.mid, b0.cout, b0.stride, b0.skip)) {
-            TRY(smirk_encoder_head_fused_split16(img, (const float*)w->stem.w, w->stem.scale, w->stem.shift, (const float*)b0.dw.w, b0.dw.scale, b0.dw.shift,
-                                                 b0.pw.w, b0.pw.scale, b0.pw.shift, b0.skip ? 1 : 0, x, B, H, W, b0.stride, stream));
-            h = (h + b0.stride - 1) / b0.stride; wd = (wd + b0.stride - 1) / b0.stride;
-            first_block = 1;
-        }
-    }
-    if (!first_block)
-    TRY(split ? smirk_stem_conv_s2_split16(img, (const float*)w->stem.w, w->stem.scale, w->stem.shift, x, B, H, W, w->stem_cout, stream)
-              : smirk_stem_conv_s2(img, (const float*)w->stem.w, w->stem.scale, w->stem.shift, (float*)x, B, H, W, w->stem_cout, stream));
+    Rot rot;
+    for (int i = 0; i < 3; ++i) rot.slot[i] = (char*)ws + p.slot_off[i];
+    float* pooled = (float*)((char*)ws + p.pooled_off);
     auto pointwise = [&](const void* in, int hh, int ww, int cin, int cout, const SmirkConvLayer& L, bool relu, const void* res, void* o) {
         return conv_call(split, desc1x1(B, hh, ww, cin, cout, relu, false), in, nullptr, L, res, o, stream);
     };
@@ -426,62 +458,57 @@ extern "C" int smirk_backbone_forward(const SmirkBackboneWeights* w, const float
         return split ? smirk_dwconv3x3_split16(in, (const float*)L.w, L.scale, L.shift, o, B, hh, ww, c, stride, 1, stream)
                      : smirk_dwconv3x3((const float*)in, (const float*)L.w, L.scale, L.shift, (float*)o, B, hh, ww, c, stride, 1, stream);
     };
-    int c = first_block ? w->blocks[0].cout : w->stem_cout;
-    for (int i = first_block; i < w->n_blocks; ++i) {
-        const SmirkMbBlock& b = w->blocks[i];
-        if (b.cin != c) return SMIRK_ERR_BAD_ARG;
-        const int ho = (h + b.stride - 1) / b.stride, wo = (wd + b.stride - 1) / b.stride;
-        const void* res = b.skip ? x : nullptr;
-        if (b.kind == 2) {                                          // ConvBnAct 1x1
-            void* o = p.rot.pick(x, nullptr);
-            TRY(pointwise(x, h, wd, b.cin, b.cout, b.pw, true, nullptr, o));
-            x = o;
-        } else if (split && !no_fuse && !no_image && !no_tile && b.kind == 1 && b.cin <= 48 && smirk_mbconv_image_supported(h, wd, b.cin, b.mid, b.cout, b.stride)) {
-            // stride-1 blocks of the 56 x 56 / 28 x 28 stages (14 x 14 halo tiles) and of the small backbone's 14 x 14 stage (whole images), 24-48 channels:
-            // the image-resident kernel instead of the 8 x 8-tile kernel below (round 5)
-            void* o = p.rot.pick(x, nullptr);
-            TRY(smirk_mbconv_image_split16(x, b.pw.w, b.pw.scale, b.pw.shift, (const float*)b.dw.w, b.dw.scale, b.dw.shift, b.pwl.w, b.pwl.scale, b.pwl.shift,
-                                           b.skip ? 1 : 0, o, B, h, wd, b.cin, b.mid, b.cout, stream));
-            x = o;
-        } else if (split && !no_fuse && b.kind == 1 && b.stride == 2 && !b.skip && smirk_mbconv_s2_supported(b.cin, b.mid, b.cout)) {
-            void* o = p.rot.pick(x, nullptr);                       // stride-2 blocks down to 14 x 14: one wave per 4 x 8 output tile (mbconv_s2.hip), same bits as the kernel below
-            TRY(smirk_mbconv_s2_split16(x, b.pw.w, b.pw.scale, b.pw.shift, (const float*)b.dw.w, b.dw.scale, b.dw.shift, b.pwl.w, b.pwl.scale, b.pwl.shift,
-                                        o, B, h, wd, b.cin, b.mid, b.cout, stream));
-            x = o;
-        } else if (split && !no_fuse && (b.kind == 1 || fuse_ds) && smirk_mbconv_supported(b.cin, b.mid, b.cout, b.stride)) {
-            void* o = p.rot.pick(x, nullptr);
-            const SmirkConvLayer& proj = b.kind == 1 ? b.pwl : b.pw;
-            TRY(smirk_mbconv_fused_split16(x, b.kind == 1 ? b.pw.w : nullptr, b.kind == 1 ? b.pw.scale : nullptr, b.kind == 1 ? b.pw.shift : nullptr,
-                                           (const float*)b.dw.w, b.dw.scale, b.dw.shift, proj.w, proj.scale, proj.shift, b.skip ? 1 : 0, o, B, h, wd,
-                                           b.cin, b.mid, b.cout, b.stride, stream));
-            x = o;
-        } else if (split && !no_fuse && !no_image && b.kind == 1 && smirk_mbconv_image_supported(h, wd, b.cin, b.mid, b.cout, b.stride)) {
-            void* o = p.rot.pick(x, nullptr);                       // <= 14 x 14, 80-112 channels: whole images per workgroup (mbconv_image.hip)
-            TRY(smirk_mbconv_image_split16(x, b.pw.w, b.pw.scale, b.pw.shift, (const float*)b.dw.w, b.dw.scale, b.dw.shift, b.pwl.w, b.pwl.scale, b.pwl.shift,
-                                           b.skip ? 1 : 0, o, B, h, wd, b.cin, b.mid, b.cout, stream));
-            x = o;
-        } else if (b.kind == 0) {                                   // DepthwiseSeparable: dw + BN + ReLU -> pw + BN (+ x)
-            void* t = p.rot.pick(x, nullptr);
-            TRY(depthwise(x, h, wd, b.cin, b.stride, b.dw, t));
-            void* o = p.rot.pick(x, t);
-            TRY(pointwise(t, ho, wo, b.cin, b.cout, b.pw, false, res, o));
-            x = o;
-        } else {                                                    // InvertedResidual: pw + BN + ReLU -> dw + BN + ReLU -> pwl + BN (+ x)
-            void* t = p.rot.pick(x, nullptr);
-            TRY(pointwise(x, h, wd, b.cin, b.mid, b.pw, true, nullptr, t));
-            void* u = p.rot.pick(x, t);
-            TRY(depthwise(t, h, wd, b.mid, b.stride, b.dw, u));
-            void* o = p.rot.pick(x, u);
-            TRY(pointwise(u, ho, wo, b.mid, b.cout, b.pwl, false, res, o));
-            x = o;
-        }
-        h = ho; wd = wo; c = b.cout;
+    void* x = nullptr;                                  // the current activation: none yet where the fused head reads the image itself
+    if (p.blk[0].family != SMIRK_BACKBONE_HEAD_FUSED) {
+        x = rot.slot[0];
+        TRY(split ? smirk_stem_conv_s2_split16(img, (const float*)w->stem.w, w->stem.scale, w->stem.shift, x, B, H, W, w->stem_cout, stream)
+                  : smirk_stem_conv_s2(img, (const float*)w->stem.w, w->stem.scale, w->stem.shift, (float*)x, B, H, W, w->stem_cout, stream));
     }
-    if (c != w->feat_ch) return SMIRK_ERR_BAD_ARG;
-    if (feat_out) (void)hipMemcpyAsync(feat_out, x, act_bytes(B, h, wd, c), hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    for (int i = 0; i < w->n_blocks; ++i) {
+        const SmirkMbBlock& b = w->blocks[i];
+        const BackbonePlan::Block& q = p.blk[i];
+        const void* res = b.skip ? x : nullptr;
+        void* t = rot.pick(x, nullptr);                 // the two slots that do not hold x: temporaries of the unfused sequences, one of them the output
+        void* u = rot.pick(x, t);
+        void* o = t;
+        switch (q.family) {
+            case SMIRK_BACKBONE_HEAD_FUSED:
+                TRY(smirk_encoder_head_fused_split16(img, (const float*)w->stem.w, w->stem.scale, w->stem.shift, (const float*)b.dw.w, b.dw.scale, b.dw.shift,
+                                                     b.pw.w, b.pw.scale, b.pw.shift, b.skip ? 1 : 0, o, B, H, W, b.stride, stream));
+                break;
+            case SMIRK_BACKBONE_CONV1X1:
+                TRY(pointwise(x, q.h, q.w, b.cin, b.cout, b.pw, true, nullptr, o));
+                break;
+            case SMIRK_BACKBONE_MBCONV_IMAGE:
+                TRY(smirk_mbconv_image_split16(x, b.pw.w, b.pw.scale, b.pw.shift, (const float*)b.dw.w, b.dw.scale, b.dw.shift, b.pwl.w, b.pwl.scale, b.pwl.shift,
+                                               b.skip ? 1 : 0, o, B, q.h, q.w, b.cin, b.mid, b.cout, stream));
+                break;
+            case SMIRK_BACKBONE_MBCONV_S2:
+                TRY(smirk_mbconv_s2_split16(x, b.pw.w, b.pw.scale, b.pw.shift, (const float*)b.dw.w, b.dw.scale, b.dw.shift, b.pwl.w, b.pwl.scale, b.pwl.shift,
+                                            o, B, q.h, q.w, b.cin, b.mid, b.cout, stream));
+                break;
+            case SMIRK_BACKBONE_MBCONV_TILE:
+                TRY(smirk_mbconv_fused_split16(x, b.pw.w, b.pw.scale, b.pw.shift, (const float*)b.dw.w, b.dw.scale, b.dw.shift, b.pwl.w, b.pwl.scale, b.pwl.shift,
+                                               b.skip ? 1 : 0, o, B, q.h, q.w, b.cin, b.mid, b.cout, b.stride, stream));
+                break;
+            case SMIRK_BACKBONE_DS_UNFUSED:             // dw + BN + ReLU -> pw + BN (+ x)
+                o = u;
+                TRY(depthwise(x, q.h, q.w, b.cin, b.stride, b.dw, t));
+                TRY(pointwise(t, q.ho, q.wo, b.cin, b.cout, b.pw, false, res, o));
+                break;
+            default:                                    // SMIRK_BACKBONE_IR_UNFUSED: pw + BN + ReLU -> dw + BN + ReLU -> pwl + BN (+ x)
+                TRY(pointwise(x, q.h, q.w, b.cin, b.mid, b.pw, true, nullptr, t));
+                TRY(depthwise(t, q.h, q.w, b.mid, b.stride, b.dw, u));
+                TRY(pointwise(u, q.ho, q.wo, b.mid, b.cout, b.pwl, false, res, o));
+                break;
+        }
+        x = o;
+    }
+    const int hw = p.blk[w->n_blocks - 1].ho * p.blk[w->n_blocks - 1].wo, c = w->feat_ch;
+    if (feat_out) (void)hipMemcpyAsync(feat_out, x, (size_t)B * hw * c * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
     if (w->n_out == 0) return SMIRK_OK;
-    TRY(split ? smirk_gap_linear_split16(x, w->head_w, w->head_b, out, p.pooled, B, h * wd, c, w->n_out, stream)
-              : smirk_gap_linear((const float*)x, w->head_w, w->head_b, out, p.pooled, B, h * wd, c, w->n_out, stream));
+    TRY(split ? smirk_gap_linear_split16(x, w->head_w, w->head_b, out, pooled, B, hw, c, w->n_out, stream)
+              : smirk_gap_linear((const float*)x, w->head_w, w->head_b, out, pooled, B, hw, c, w->n_out, stream));
     if (w->clamp_n_exp >= 0) TRY(smirk_expression_clamps(out, B, w->clamp_n_exp, stream));
     return SMIRK_OK;
 }

@@ -10,11 +10,12 @@
 // SMIRK_CONV_RING                   "0": 0, the 64-output-channel ring kernels off (round-3 kernels); anything else: 1     1               tests/test_conv_gpu.py
 // SMIRK_DISABLE_PATCH_KERNEL        set (any value, "0" too): 1, neither the patch nor the ring convolution kernels        0               (integrators)
 // SMIRK_DISABLE_ENC1_FUSED          set (any value): 1, smirk_enc1_fused_supported answers 0                              0               tests/test_conv_gpu.py
-// SMIRK_DISABLE_MBCONV_IMAGE        set (any value): 1, no image-resident MBConv kernel in the encoder backbone           0               tests/test_encoder_gpu.py
-// SMIRK_DISABLE_MBCONV_TILE         set (any value): 1, the 24-48-channel stride-1 blocks stay on mbconv_fused_kernel     0               tests/test_encoder_gpu.py
-// SMIRK_DISABLE_MBCONV_FUSED        set (any value): 1, no fused MBConv kernels (separate expand / depthwise / project)   0               tests/test_encoder_gpu.py
-//                                   (smirk_encoder.py reads it too, for its own fused-block path)
-// SMIRK_DISABLE_ENCODER_HEAD_FUSED  set (any value): 1, stem and first block of the backbone as separate launches         0               tests/test_encoder_gpu.py
+// The next four reach backbone_plan (network.hip) as one struct of values; its priority table says what each takes away:
+// SMIRK_DISABLE_MBCONV_IMAGE        set (any value): 1, no image-resident MBConv kernel in the encoder backbone           0               tests/test_encoder_gpu.py,
+// SMIRK_DISABLE_MBCONV_TILE         set (any value): 1, blocks that mbconv_fused_kernel (8 x 8 tiles) also serves stay    0               tests/test_backbone_
+//                                   on it instead of the image-resident kernel: the 24-48-channel stride-1 blocks                         dispatch_{cpu,gpu}.py
+// SMIRK_DISABLE_MBCONV_FUSED        set (any value): 1, no fused MBConv kernels (separate expand / depthwise / project)   0
+// SMIRK_DISABLE_ENCODER_HEAD_FUSED  set (any value): 1, stem and first block of the backbone as separate launches         0
 // SMIRK_GEN_SPLIT_CHAINS            the number of the generator's H/8 + H/16 sub-batch chains: "0": 1, "3": 3, else 2     0 (unset):      tests/test_generator_gpu.py,
 //                                                                                                                         heuristic       bench.py
 // SMIRK_WGRAD_F16                   atoi(value): 0 exact-fp32 weight-gradient kernel, 1 / 2 split-fp16 x3 with 1 / 2       2               tests/test_train_ops_gpu.py

@@ -220,88 +220,10 @@ class MobileNetV3Features(nn.Module):
             feat = L.loud_cut("smirk_amd encoder forward", feat, deps)
         return out, feat
 
-    def _pointwise(self, lib, st, x, pk, relu, residual=None):
-        w, sc, sh = pk
-        B, H, W, C = x.shape
-        d = L.SmirkConvDesc()
-        d.B, d.H, d.W, d.C0, d.C1, d.Cout = B, H, W, C, 0, w.shape[0]
-        d.KH = d.KW = d.stride = 1
-        d.pad_t = d.pad_l = 0
-        d.Ho, d.Wo, d.pad_mode = H, W, L.PAD_ZERO
-        d.act, d.out_mode = (L.ACT_RELU if relu else L.ACT_NONE), L.OUT_NHWC
-        out = torch.empty(B, H, W, w.shape[0], device=x.device)
-        P = L.ptr
-        fn = lib.smirk_conv_igemm_f16x3 if self._split else lib.smirk_conv_igemm_f32
-        L.check(fn(d, P(x), None, P(w), P(sc), P(sh), P(residual, allow_none=True), P(out), st))
-        return out
-
-    def _depthwise(self, lib, st, x, pk, stride):
-        w, sc, sh = pk
-        B, H, W, C = x.shape
-        out = torch.empty(B, (H + stride - 1) // stride, (W + stride - 1) // stride, C, device=x.device)
-        P = L.ptr
-        L.check((lib.smirk_dwconv3x3_split16 if self._split else lib.smirk_dwconv3x3)(P(x), P(w), P(sc), P(sh), P(out), B, H, W, C, stride, 1, st))
-        return out
-
-    @staticmethod
-    def _fusable(lib, cin, pk, blk):
-        if blk.kind == "ds":
-            return False        # measured: no expanded tensor to keep on chip, the two streaming kernels are as fast (s1) or faster (s2)
-        return bool(lib.smirk_mbconv_supported(cin, pk["dw"][0].shape[1], pk["pw" if blk.kind == "ds" else "pwl"][0].shape[0], blk.stride))
-
-    def _fused_block(self, lib, st, x, pk, blk):
-        """whole DS / IR block in one launch (csrc/mbconv.hip): the expanded activations stay in LDS"""
-        B, H, W, C = x.shape
-        P, N = L.ptr, (lambda t: L.ptr(t, allow_none=True))
-        if blk.kind == "ds":
-            (wd, s2, b2), (wp, s3, b3) = pk["dw"], pk["pw"]
-            we = s1 = b1 = None
-        else:
-            (we, s1, b1), (wd, s2, b2), (wp, s3, b3) = pk["pw"], pk["dw"], pk["pwl"]
-        mid, cout, s = wd.shape[1], wp.shape[0], blk.stride
-        out = torch.empty(B, (H + s - 1) // s, (W + s - 1) // s, cout, device=x.device)
-        if blk.kind == "ir" and s == 2 and not blk.skip and lib.smirk_mbconv_s2_supported(C, mid, cout):
-            # one wave per output tile (csrc/mbconv_s2.hip), as smirk_backbone_forward dispatches it
-            L.check(lib.smirk_mbconv_s2_split16(P(x), P(we), P(s1), P(b1), P(wd), P(s2), P(b2), P(wp), P(s3), P(b3), P(out), B, H, W, C, mid, cout, st))
-            return out
-        L.check(lib.smirk_mbconv_fused_split16(P(x), N(we), N(s1), N(b1), P(wd), P(s2), P(b2), P(wp), P(s3), P(b3), int(bool(blk.skip)),
-                                               P(out), B, H, W, C, mid, cout, s, st))
-        return out
-
-    def forward(self, img, _taps=None):
+    def forward(self, img):
         """img [B,3,H,W] NCHW in [0,1] -> last feature map NHWC [B,H/32,W/32,C] (fp32, or split16 storage when PRECISION == "f16x3":
-        see `features_f32`).  `_taps` (list) collects the stem output and every block's output (debugging / parity tools)."""
-        if _taps is None:
-            return self.run(img, want_features=True)[1]
-        # per-layer schedule driven from Python: the debugging twin of smirk_backbone_forward (same kernels, same order), kept for `_taps`
-        if self.training:
-            raise L.SmirkHipError("the per-layer debugging schedule is eval-mode only; train mode runs through the encoders' forward (encoder_train.py)")
-        lib, st, P = L.lib(), L.stream_ptr(), self._pack()
-        img = L.as_f32c(img)
-        B, _, H, W = img.shape
-        w, sc, sh = P["stem"]
-        x = torch.empty(B, (H + 1) // 2, (W + 1) // 2, 16, device=img.device)
-        L.check((lib.smirk_stem_conv_s2_split16 if self._split else lib.smirk_stem_conv_s2)(L.ptr(img), L.ptr(w), L.ptr(sc), L.ptr(sh), L.ptr(x), B, H, W, 16, st))
-        fused = self._split and not os.environ.get("SMIRK_DISABLE_MBCONV_FUSED")
-        if _taps is not None:
-            _taps.append(("stem", x))
-        for si, stg in enumerate(self.blocks):
-            for bi, blk in enumerate(stg):
-                pk = P[(si, bi)]
-                if fused and blk.kind in ("ds", "ir") and self._fusable(lib, x.shape[3], pk, blk):
-                    x = self._fused_block(lib, st, x, pk, blk)
-                elif blk.kind == "ds":
-                    y = self._depthwise(lib, st, x, pk["dw"], blk.stride)
-                    x = self._pointwise(lib, st, y, pk["pw"], relu=False, residual=x if blk.skip else None)
-                elif blk.kind == "ir":
-                    y = self._pointwise(lib, st, x, pk["pw"], relu=True)
-                    y = self._depthwise(lib, st, y, pk["dw"], blk.stride)
-                    x = self._pointwise(lib, st, y, pk["pwl"], relu=False, residual=x if blk.skip else None)
-                else:
-                    x = self._pointwise(lib, st, x, pk["pw"], relu=True)
-                if _taps is not None:
-                    _taps.append((f"block{si}.{bi}:{blk.kind}", x))
-        return x
+        see `features_f32`)."""
+        return self.run(img, want_features=True)[1]
 
 
 def features_f32(backbone, feat):
