@@ -176,17 +176,23 @@ enum { SMIRK_ACT_NONE = 0, SMIRK_ACT_RELU = 1 };
 enum { SMIRK_OUT_NHWC = 0, SMIRK_OUT_CONVT2X2 = 1 };
 
 typedef struct SmirkConvDesc {
-    int32_t B, H, W;        /* input spatial size                                                               */
+    int32_t B, H, W;        /* input spatial size; H, W <= 32767                                                */
     int32_t C0, C1;         /* channels of source 0 and (optional, concat along C) source 1; both % 4 == 0        */
     int32_t Cout;           /* output channels (for CONVT2X2: channels per output pixel)                        */
     int32_t KH, KW;         /* 3x3 or 1x1                                                                       */
-    int32_t stride;         /* 1 (2 is accepted for 1x1 / 3x3 with the pads below)                              */
-    int32_t pad_t, pad_l;   /* leading pads; trailing pads follow from Ho, Wo                                    */
+    int32_t stride;         /* 1, or 2 for 1x1 / 3x3 on the implicit GEMM (tests/conv_cases.py runs both forms)  */
+    int32_t pad_t, pad_l;   /* leading pads, any value under zero padding, 0 or 1 under reflect; trailing pads   */
+                            /* follow from Ho, Wo                                                               */
     int32_t Ho, Wo;         /* output spatial size (CONVT2X2: the GEMM grid = input grid, output is 2H x 2W)    */
     int32_t pad_mode;       /* SMIRK_PAD_*                                                                      */
     int32_t act;            /* SMIRK_ACT_*  (applied after scale/shift and residual add)                         */
     int32_t out_mode;       /* SMIRK_OUT_*                                                                      */
 } SmirkConvDesc;
+/* Geometry, exactly (tests/conv_cases.py conv_ref64 is this paragraph in float64): tap (ky, kx) of output pixel (oy, ox) reads input row
+ * iy = oy * stride - pad_t + ky and column ix = ox * stride - pad_l + kx, for every oy < Ho, ox < Wo the caller asks for.  SMIRK_PAD_ZERO: a tap with iy outside
+ * [0, H) or ix outside [0, W) contributes zero, however far outside.  SMIRK_PAD_REFLECT: iy = -1 reads row 1 and iy = H reads row H - 2 (columns alike), and that
+ * one pixel is all the reach there is: H, W >= 2, pad_t, pad_l <= 1, (Ho - 1) * stride - pad_t + KH - 1 <= H and the same for columns, anything else returns
+ * SMIRK_ERR_UNSUPPORTED.  So does a descriptor whose H, W, (Ho - 1) * stride - pad_t or (Wo - 1) * stride - pad_l exceeds 32767 (the kernels stage row coordinates in 16 bits). */
 
 /* out = act( (conv(cat(in0,in1), w)) * scale[n] + shift[n] + residual ).
  * w: [N][K] with K = KH*KW*(C0+C1) ordered (ky,kx,c) and N = Cout (CONVT2X2: N = 4*Cout ordered (dy,dx,co), K = C0);

@@ -710,7 +710,14 @@ static int conv_dispatch_one(const SmirkConvDesc* d, const void* in0, const void
         (d->C1 > 0 && !in1) || d->Ho <= 0 || d->Wo <= 0 || d->stride <= 0 || (split && d->Cout % 8))
         return SMIRK_ERR_BAD_ARG;
     if (!((d->KH == 3 && d->KW == 3) || (d->KH == 1 && d->KW == 1))) return SMIRK_ERR_UNSUPPORTED;
-    if (d->pad_mode == SMIRK_PAD_REFLECT && (d->H < 2 || d->W < 2 || d->pad_t > 1 || d->pad_l > 1)) return SMIRK_ERR_UNSUPPORTED;
+    // conv_tile packs the first-tap coordinates of a staged row (oy * stride - pad_t, ox * stride - pad_l) into 16 bits each (`pyx`)
+    const long long iy_last = (long long)(d->Ho - 1) * d->stride - d->pad_t, ix_last = (long long)(d->Wo - 1) * d->stride - d->pad_l;
+    if (d->H > 32767 || d->W > 32767 || iy_last > 32767 || ix_last > 32767 || d->pad_t > 32767 || d->pad_l > 32767 || d->pad_t < -32767 || d->pad_l < -32767)
+        return SMIRK_ERR_UNSUPPORTED;
+    // reflect padding: one pixel of reach on every side (reflect_idx folds once): the first tap starts at most one pixel before the image (pad <= 1) and
+    // the last tap of the last output row / column ends at most one pixel after it
+    if (d->pad_mode == SMIRK_PAD_REFLECT && (d->H < 2 || d->W < 2 || d->pad_t > 1 || d->pad_l > 1 || iy_last + d->KH - 1 > d->H || ix_last + d->KW - 1 > d->W))
+        return SMIRK_ERR_UNSUPPORTED;
     ConvArgs a;
     a.d = *d; a.in0 = (const float*)in0; a.in1 = (const float*)in1; a.w = (const float*)w; a.scale = scale; a.shift = shift;
     a.residual = (const float*)residual; a.out = (float*)out;

@@ -68,6 +68,30 @@ def test_convolution_entries(lib):
     assert tail(_desc(Cout=64, act=L.ACT_RELU), P, None, P, P, P, P, P, P, 3, None) == BAD_ARG      # the fused tail is defined for the 32-channel last block only
 
 
+@pytest.mark.parametrize("entry", ["smirk_conv_igemm_f16x3", "smirk_conv_igemm_f16x1", "smirk_conv_igemm_f32"])
+def test_convolution_refuses_geometries_no_kernel_computes(lib, entry):
+    """include/smirk_hip.h, SmirkConvDesc: reflect padding reaches ONE pixel past either edge (reflect_idx folds once), and the K walks stage a row's first-tap
+    coordinates in 16 bits each.  A descriptor outside either limit is refused before anything is launched, whatever the entry."""
+    f = getattr(lib, entry)
+    call = lambda **kw: f(_desc(**kw), P, None, P, None, None, None, P, None)
+    R = dict(pad_mode=L.PAD_REFLECT)
+    # reflect: the last tap of the last output row / column may end one pixel after the image, not two
+    assert call(Ho=17, **R) == UNSUPPORTED and call(Wo=17, **R) == UNSUPPORTED                 # a 17th output row of a 16-row image at stride 1, pad 1
+    assert call(stride=2, Ho=9, Wo=8, **R) == UNSUPPORTED and call(stride=2, Ho=8, Wo=9, **R) == UNSUPPORTED     # stride 2: rows 15, 16, 17
+    assert call(H=9, W=7, stride=2, Ho=5, Wo=5, **R) == UNSUPPORTED
+    assert call(pad_t=2, **R) == UNSUPPORTED and call(pad_l=2, **R) == UNSUPPORTED and call(H=1, Ho=1, **R) == UNSUPPORTED      # (refused before this change too)
+    assert call(KH=1, KW=1, pad_t=0, pad_l=0, Ho=18, **R) == UNSUPPORTED                       # a 1 x 1 tap on row H + 1
+    # 16-bit staged coordinates
+    assert call(H=32768, Ho=32768) == UNSUPPORTED and call(W=32768, Wo=32768) == UNSUPPORTED
+    assert call(KH=1, KW=1, pad_t=0, pad_l=0, H=40000, Ho=40000, W=1, Wo=1, C0=8, Cout=8) == UNSUPPORTED
+    assert call(Ho=32770) == UNSUPPORTED and call(Wo=32770) == UNSUPPORTED                     # zero padding: output rows far past the image stage row 32768
+    assert call(stride=3, Ho=11000, Wo=16) == UNSUPPORTED
+    assert call(pad_t=40000) == UNSUPPORTED and call(pad_l=-40000) == UNSUPPORTED
+    # the statistics entry shares the dispatcher
+    rows = C.c_int(-1)
+    assert lib.smirk_conv_igemm_stats_split16(_desc(Ho=17, **R), P, None, P, P, P, C.byref(rows), 0, None) == UNSUPPORTED and rows.value == 0
+
+
 def test_flame_and_renderer_reject_missing_model(lib):
     fargs = [0 if t in (L._i, L._sz) else None for t in L._SIGS["smirk_flame_forward"][1][2:]]
     assert lib.smirk_flame_forward(None, 4, *fargs) == BAD_ARG
