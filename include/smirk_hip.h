@@ -265,7 +265,9 @@ int smirk_stem_conv_s2(const float* img_nchw, const float* w /*[Cout][27] (ky,kx
 /* depthwise 3x3, stride 1 (pad 1) or 2 (TF-'same': pad 0 top/left, 1 bottom/right for even H), + scale/shift + ReLU. NHWC. */
 int smirk_dwconv3x3(const float* in, const float* w /*[9][C]*/, const float* scale, const float* shift, float* out,
                     int B, int H, int W, int C, int stride, int relu, void* stream);
-/* global average pool over HW then Linear: feat[B][HW][C] -> out[B][N] = mean_hw(feat) . Wt[N][C] + bias; ws = [B][C] floats of scratch. */
+/* global average pool over HW then Linear: feat[B][HW][C] -> out[B][N] = mean_hw(feat) . Wt[N][C] + bias; ws = [B][C] floats of scratch, left holding the pooled
+ * vectors (two launches).  ws may be NULL for N <= 64: the same outputs, bit for bit, from ONE launch that keeps no pooled vectors (a caller without a head weight
+ * gradient: smirk_amd/encoder_eval_grad.py). */
 int smirk_gap_linear(const float* feat, const float* w, const float* bias, float* out, float* ws, int B, int HW, int C, int N,
                      void* stream);
 /* split16 variants of the three encoder ops (activations in the split-fp16 format of smirk_conv_igemm_f16x3; weights / scale / shift fp32;
@@ -546,9 +548,26 @@ int smirk_dwconv3x3_wgrad_split16(const void* dz, const void* x, float* dw, int 
 /* the same gradient written in the parameter's own layout [C][1][3][3] (conv_dw.weight of the timm blocks: no transpose-copy between backward and Adam) */
 int smirk_dwconv3x3_wgrad_param_split16(const void* dz, const void* x, float* dw, int B, int H, int W, int C, int stride, void* ws, size_t ws_bytes, void* stream);
 /* F.adaptive_avg_pool2d(features, 1) + nn.Linear backward (smirk_encoder.py:18-22): dout [B][N], w [N][C], pooled [B][C] (the forward's workspace) ->
- * dw [N][C], db [N] (both or neither), dfeat split16 [B][HW][C] (nullable) */
+ * dw [N][C], db [N] (both or neither; pooled may be NULL with neither), dfeat split16 [B][HW][C] (nullable) */
 int smirk_gap_linear_backward_split16(const float* dout, const float* w, const float* pooled, float* dw, float* db, void* dfeat, int B, int HW, int C, int N,
                                       void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Image gradient through a FROZEN backbone in .eval() (csrc/encoder_eval_grad.hip; smirk_amd/encoder_eval_grad.py) — the even steps of the reference's
+ * training run (base_trainer.py:258-268 `freeze_encoder_in_second_path`; smirk_trainer.py:367-368 freeze_module = requires_grad_(False) + .eval();
+ * :300, :375 the cycle loss back-propagated through the frozen encoder into the generator).  BatchNorm works from the running statistics: in the
+ * backward it is the per-channel factor s[c] = gamma / sqrt(running_var + eps), a ReLU is the mask [y > 0] of the unit's stored OUTPUT (y == 0 counts
+ * as masked), and no parameter has a gradient.  Activations / gradients split16 NHWC, s / w fp32.  Every pointer 16-byte aligned; tensors of 2 GiB and
+ * more are refused with SMIRK_ERR_UNSUPPORTED (32-bit indexing).
+ *
+ * smirk_dwconv3x3_eval_backward_split16 — mask of the depthwise unit, depthwise data gradient and the mask of the unit BEFORE it in one launch:
+ *   dx[b,iy,ix,c] = (add + sum_taps dy[o] * s_out[c] * [y_out[o] > 0] * w[ky,kx,c]) * (y_in ? s_in[c] * [y_in[b,iy,ix,c] > 0] : 1)
+ * dy, y_out [B][ceil(H/s)][ceil(W/s)][C]; add (nullable: the skip gradient), y_in (nullable, with s_in), dx [B][H][W][C]; w [9][C]; tap geometry and
+ * TF-'SAME' leading pads of smirk_dwconv3x3_dgrad_split16.
+ * smirk_relu_scale_backward_split16 — dz[m][c] = dy[m][c] * s[c] * [y[m][c] > 0] over [M][C]. */
+int smirk_dwconv3x3_eval_backward_split16(const void* dy, const void* y_out, const float* s_out, const float* w, const void* add, const void* y_in,
+                                          const float* s_in, void* dx, int B, int H, int W, int C, int stride, void* stream);
+int smirk_relu_scale_backward_split16(const void* dy, const void* y, const float* s, void* dz, long long M, int C, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Launch profiler (diagnostics; the one place where the library creates HIP events and synchronises — on request only).

@@ -11,7 +11,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libsmirk_hip.so")
 LIB_PATH = os.environ.get("SMIRK_HIP_LIBRARY", LIB_PATH)      # tuning aid: A/B a differently-built libsmirk_hip.so in one gpurun
-ABI_VERSION = 16
+ABI_VERSION = 17
 PACK_DEPTHWISE, PACK_STEM, PACK_CONVT2X2 = -3, -27, -2          # SmirkPackJob.KH markers (include/smirk_hip.h SMIRK_PACK_*)
 SMIRK_OK, SMIRK_ERR_BAD_ARG, SMIRK_ERR_WORKSPACE, SMIRK_ERR_LAUNCH, SMIRK_ERR_UNSUPPORTED = 0, -1, -2, -3, -4      # include/smirk_hip.h
 
@@ -185,6 +185,8 @@ _SIGS = {
     "smirk_dwconv3x3_wgrad_split16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _sz, _p]),
     "smirk_dwconv3x3_wgrad_param_split16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _sz, _p]),
     "smirk_gap_linear_backward_split16": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "smirk_dwconv3x3_eval_backward_split16": (_i, [_p] * 8 + [_i] * 5 + [_p]),
+    "smirk_relu_scale_backward_split16": (_i, [_p, _p, _p, _p, C.c_longlong, _i, _p]),
     "smirk_profile_start": (_i, []),
     "smirk_profile_stop": (_i, [C.POINTER(SmirkProfileRecord), _i]),
     "smirk_random_point_budget": (_i, [_p, _i, _i, C.c_float, C.c_uint64, C.c_uint64, _p]),

@@ -20,7 +20,7 @@ extern "C" const char* smirk_strerror(int code) {
     }
 }
 
-extern "C" int smirk_abi_version(void) { return 16; }
+extern "C" int smirk_abi_version(void) { return 17; }
 
 // ---- environment switches (switches.h: names, values, defaults) -------------------------------------------------------------------------
 int smirk_switch(SmirkSwitch s) {

@@ -200,7 +200,7 @@ extern "C" int smirk_dwconv3x3(const float* in, const float* w, const float* sca
     return smirk_launch_status();
 }
 
-// global-average-pool + Linear head in two launches: (1) pooled[b][c] = mean over HW — one workgroup per (face, 256-channel slab), lanes over
+// global-average-pool + Linear head in two launches (one when the caller passes no `ws`, below): (1) pooled[b][c] = mean over HW — one workgroup per (face, 256-channel slab), lanes over
 // channels so every load is coalesced; (2) out[b][n] = pooled[b] . W[n] + bias — grid (n-tile of 64, face), one wave per output neuron,
 // lane-strided dot product + shuffle reduction.  `ws` holds the pooled vectors ([B][C] floats).
 __global__ __launch_bounds__(256) void gap_pool_kernel(const float* __restrict__ feat, float* __restrict__ pooled, int HW, int C, int split) {
@@ -235,9 +235,55 @@ __global__ __launch_bounds__(256) void gap_linear_kernel(const float* __restrict
     }
 }
 
+// The same head in ONE launch, for a caller that does not need the pooled vectors afterwards (ws == NULL: a frozen head has no weight gradient) and N <= 64 (the
+// pose and expression heads): with a single n-tile per face the block that pools is the only block that consumes the pooled vector, so nothing is pooled twice
+// (with more tiles every tile would pool the whole face again).  Channel c is summed over the pixels in the same order by the same expressions as gap_pool_kernel,
+// four channels of a thread at a time so their loads are independent, and the Linear part is gap_linear_kernel's: bit-identical outputs.
+__global__ __launch_bounds__(256) void gap_pool_linear_kernel(const float* __restrict__ feat, const float* __restrict__ w, const float* __restrict__ bias,
+                                                              float* __restrict__ out, int HW, int C, int N, int split) {
+    extern __shared__ float pooled[];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* f = feat + (size_t)b * HW * C;
+    const _Float16* h = (const _Float16*)f;
+    for (int c0 = tid; c0 < C; c0 += 1024) {
+        float s[4] = {0.f, 0.f, 0.f, 0.f};
+        int off[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = c0 + 256 * j;
+            off[j] = c >= C ? -1 : (split ? (c >> 3) * 16 + (c & 7) : c);
+        }
+        for (int p = 0; p < HW; ++p)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (off[j] >= 0) {
+                    if (split) s[j] += enc_join(h[(size_t)p * C * 2 + off[j]], h[(size_t)p * C * 2 + off[j] + 8]);
+                    else s[j] += f[(size_t)p * C + off[j]];
+                }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = c0 + 256 * j;
+            if (c < C) pooled[c] = s[j] / (float)HW;
+        }
+    }
+    __syncthreads();
+    for (int n = wave; n < N; n += 4) {
+        const float* wr = w + (size_t)n * C;
+        float s = 0.f;
+        for (int c = lane; c < C; c += 64) s = fmaf(pooled[c], wr[c], s);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (lane == 0) out[(size_t)b * N + n] = s + (bias ? bias[n] : 0.f);
+    }
+}
+
 static int gap_launch(const float* feat, const float* w, const float* bias, float* out, float* ws, int B, int HW, int C, int N,
                       void* stream, int split) {
-    if (!feat || !w || !out || !ws || B <= 0 || HW <= 0 || C <= 0 || N <= 0 || C > 8192 || (split && C % 8)) return SMIRK_ERR_BAD_ARG;
+    if (!feat || !w || !out || (!ws && N > 64) || B <= 0 || HW <= 0 || C <= 0 || N <= 0 || C > 8192 || (split && C % 8)) return SMIRK_ERR_BAD_ARG;
+    if (!ws) {
+        SMIRK_LAUNCH(gap_pool_linear_kernel, dim3(B), dim3(256), (size_t)C * 4, (hipStream_t)stream, feat, w, bias, out, HW, C, N, split);
+        return smirk_launch_status();
+    }
     SMIRK_LAUNCH(gap_pool_kernel, dim3((C + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, feat, ws, HW, C, split);
     SMIRK_LAUNCH(gap_linear_kernel, dim3((N + 63) / 64, B), dim3(256), (size_t)C * 4, (hipStream_t)stream, (const float*)ws, w, bias,
                        out, C, N);

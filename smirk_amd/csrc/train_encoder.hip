@@ -419,7 +419,7 @@ extern "C" int smirk_stem_conv_s2_dgrad_split16(const void* dz, const float* w, 
 
 extern "C" int smirk_gap_linear_backward_split16(const float* dout, const float* w, const float* pooled, float* dw, float* db, void* dfeat, int B, int HW,
                                                  int C, int N, void* stream) {
-    if (!dout || !w || !pooled || B <= 0 || HW <= 0 || C <= 0 || C % 8 || N <= 0 || (!dw != !db)) return SMIRK_ERR_BAD_ARG;
+    if (!dout || !w || (!pooled && dw) || B <= 0 || HW <= 0 || C <= 0 || C % 8 || N <= 0 || (!dw != !db)) return SMIRK_ERR_BAD_ARG;     // (pooled feeds dw only)
     hipStream_t st = (hipStream_t)stream;
     if (dw) SMIRK_LAUNCH(head_wgrad_kernel, dim3((unsigned)(((size_t)N * C + 255) / 256)), dim3(256), 0, st, dout, pooled, dw, db, B, C, N);
     if (dfeat) SMIRK_LAUNCH(head_dgrad_kernel, dim3(blocks_for((size_t)B * (C / 8), 16384)), dim3(256), 0, st, dout, w, (float*)dfeat, B, HW, C, N);

@@ -16,6 +16,11 @@ exactly that sequence:
     cycle loss = mse(exp) + 10 mse(jaw) + 10 mse(eyelid) [+ mse(shape)]        smirk_trainer.py:304-313
     backward; clip_grad_norm_(generator, 0.1); optimiser steps                 smirk_trainer.py:367-376
 
+The even steps (base_trainer.py:258-268 `freeze_encoder_in_second_path = (batch_idx % 2 == 0)`; smirk_trainer.py:367-368 `freeze_module` on the three
+sub-encoders = requires_grad False + .eval()) are served too: `cycle_forward(..., freeze_generator=False)` with the sub-encoders frozen and in .eval() sends
+the cycle loss through encoder_eval_grad.py (running-statistics BatchNorm, data gradients only) into the train-mode generator; only the generator learns.
+`graph_cycle_modules` captures the train-mode path only: the even step is not captured into HIP graphs.
+
 Multi-GPU (SURVEY.md §8(e) "C2"): batch-sharded data parallel, gradients averaged with ONE bucketed RCCL all-reduce per dtype after backward
 (`allreduce_gradients`); xGMI is point-to-point, so few large buckets (default 64 MiB: the generator's 125 MB of fp32 gradients go out as two) rather than
 per-parameter calls.  BatchNorm statistics stay per rank, like torch DDP without SyncBatchNorm (the reference has no DDP wrapper at all).
@@ -119,7 +124,7 @@ def graph_cycle_modules(generator, encoder, generator_input, encoder_input, grad
     Note: replays write running_mean / running_var / num_batches_tracked from captured kernels, so torch's `_version` counters do not move; the modules'
     eval-mode weight caches (folded BatchNorm) are therefore dropped on every train() <-> eval() transition (SmirkGenerator.train,
     MobileNetV3Features.train) — call `.eval()` AFTER the last replay, as `nn.Module` users do anyway."""
-    if not (generator.training and encoder.training):
+    if not (generator.training and encoder.training and all(m.training for m in encoder.modules())):     # (frozen sub-encoders in .eval(): the even step is not captured)
         raise ValueError("graph_cycle_modules captures the TRAIN-mode path: call .train() first")
     enc = _CycleEncoder(encoder, grad_keys)
     gen = _CycleGenerator(generator)

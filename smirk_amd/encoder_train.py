@@ -2,8 +2,10 @@
 
 What the reference computes after `self.train()` (smirk_trainer.py:349-355 -> base_trainer.py:108-111) when autograd differentiates
 `self.smirk_encoder(reconstructed_img_2nd_path)` (smirk_trainer.py:297): every BatchNorm2d of the three timm `tf_mobilenetv3_*_minimal_100`
-feature extractors (smirk_encoder.py:7-12) normalises with batch statistics and updates its running estimates — frozen sub-encoders included,
-`freeze_module` only clears requires_grad — and the backward pass returns parameter gradients for the sub-encoders that are being optimised plus
+feature extractors (smirk_encoder.py:7-12) normalises with batch statistics and updates its running estimates — sub-encoders whose parameters do not
+require grad included, as long as they are in train mode: that is `step1` and the odd steps, where `self.train()` (smirk_trainer.py:352) has put every
+backbone back into train mode and nothing has frozen it since.  On the even steps `utils.freeze_module` (smirk_trainer.py:367-368; src/utils/utils.py:46-51)
+clears requires_grad AND calls `.eval()`: those backbones run encoder_eval_grad.py instead — and the backward pass returns parameter gradients for the sub-encoders that are being optimised plus
 the IMAGE gradient that the cycle loss sends back into the generator (config_train.yaml: freeze_generator_in_second_path False).
 
 One torch.autograd.Function per backbone.  Forward: bare stem / depthwise / pointwise convolutions, each followed by

@@ -198,6 +198,12 @@ class MobileNetV3Features(nn.Module):
             from .encoder_train import BackboneTrainFunction
             out = BackboneTrainFunction.apply(self, head, clamp_n_exp, img, *(list(self.parameters()) + list(head.parameters())))
             return out, None
+        if (head is not None and not want_features and PRECISION == "f16x3" and torch.is_grad_enabled() and img.requires_grad
+                and not any(p.requires_grad for p in list(self.parameters()) + list(head.parameters()))):
+            # frozen + .eval() inside an autograd graph (utils.freeze_module on the even steps, smirk_trainer.py:367-368; :300 back-propagates the cycle loss
+            # through the frozen encoder into the generator): unit-by-unit forward with a tape, data gradients only (encoder_eval_grad.py)
+            from .encoder_eval_grad import BackboneEvalGradFunction
+            return BackboneEvalGradFunction.apply(self, head, clamp_n_exp, img), None
         src = img
         img = L.as_f32c(img.detach())
         if not img.is_cuda:
