@@ -51,7 +51,7 @@ from .augment import TemplateBank, augment_flame_params, load_templates  # noqa:
 from .losses import FirstPathLoss, LossTerms, weighted_loss  # noqa: F401  (smirk_trainer.py:56-154: the first path's loss head; losses.cycle_loss: :304-313)
 from . import first_path, losses  # noqa: F401  (smirk_trainer.py:34-154 over the modules)
 from .vgg_loss import VGGPerceptualLoss  # noqa: E402,F401  (smirk_trainer.py:104: the first path's perceptual term; drop-in for src.losses.VGGPerceptualLoss)
-
+from .mica import MICA, MappingNetwork  # noqa: E402,F401  (smirk_trainer.py:128-131: the pre-training stage's shape term; drop-in for src.models.MICA.mica)
 
 
 def check_numerics():
@@ -63,4 +63,4 @@ def check_numerics():
 
 
 __all__ = ["FLAME", "Renderer", "SmirkEncoder", "SmirkGenerator", "SmirkHipError", "lib", "masking", "VideoPipeline", "check_numerics", "TemplateBank", "augment_flame_params",
-           "load_templates", "FirstPathLoss", "LossTerms", "weighted_loss", "losses", "first_path", "VGGPerceptualLoss"]
+           "load_templates", "FirstPathLoss", "LossTerms", "weighted_loss", "losses", "first_path", "VGGPerceptualLoss", "MICA", "MappingNetwork"]

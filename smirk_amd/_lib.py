@@ -204,6 +204,30 @@ _SIGS = {
 }
 EXPORTS = tuple(_SIGS)
 
+# The extension table of include/smirk_mica.h (the frozen MICA network of the pre-training stage): the same shared object, its own version.  The main table
+# above, ABI_VERSION and include/smirk_hip.h do not move when an entry is added here.
+MICA_ABI_VERSION = 1
+MICA_FC_MAX_B, MICA_HEAD_LAYERS, MICA_HEAD_MAX_DIM = 64, 5, 1024   # include/smirk_mica.h SMIRK_MICA_FC_MAX_B, SMIRK_MICA_HEAD_LAYERS, SMIRK_MICA_HEAD_MAX_DIM
+
+
+class SmirkMicaLinear(C.Structure):
+    _fields_ = [("w", _p), ("b", _p), ("n_in", C.c_int32), ("n_out", C.c_int32)]
+
+
+class SmirkMicaHead(C.Structure):
+    _fields_ = [("layer", SmirkMicaLinear * MICA_HEAD_LAYERS)]
+
+
+MICA_SIGS = {
+    "smirk_mica_abi_version": (_i, []),
+    "smirk_mica_prepare_split16": (_i, [_p, _p, _i, _i, _i, _p]),
+    "smirk_mica_affine_prelu_split16": (_i, [_p, _p, _p, _p, _p, C.c_longlong, _i, _p]),
+    "smirk_mica_fc_workspace_bytes": (_sz, [_i, _i, _i]),
+    "smirk_mica_fc_split16": (_i, [_p, _p, _p, _p, _p, _sz, _i, _i, _i, _p]),
+    "smirk_mica_head": (_i, [_p, C.POINTER(SmirkMicaHead), _p, _i, _p]),
+}
+MICA_EXPORTS = tuple(MICA_SIGS)
+
 _LIB = None
 
 
@@ -219,10 +243,11 @@ def lib():
             raise SmirkHipError(f"{LIB_PATH} not found: build it with `python -m smirk_amd.build` "
                                 "(smirk_amd has no CPU / eager fallback)")
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(L, name)           # AttributeError => header / library mismatch
-            fn.restype, fn.argtypes = res, args
-        if L.smirk_abi_version() != ABI_VERSION:
+        for table in (_SIGS, MICA_SIGS):
+            for name, (res, args) in table.items():
+                fn = getattr(L, name)       # AttributeError => header / library mismatch
+                fn.restype, fn.argtypes = res, args
+        if L.smirk_abi_version() != ABI_VERSION or L.smirk_mica_abi_version() != MICA_ABI_VERSION:
             raise SmirkHipError("libsmirk_hip.so ABI version mismatch; rebuild")
         _LIB = L
     return _LIB

@@ -13,7 +13,10 @@ The trainer itself — dataset, logging, optimiser, the `.cpu()` copies of its v
     masking.masking(img, masks, extra_points, radius, rendered_mask)  -> masked_img      smirk_trainer.py:92
     generator(cat[rendered, masked_img])                        -> reconstructed_img     smirk_trainer.py:94
     FirstPathLoss (smirk_amd.losses)                            -> loss, terms, loss_img smirk_trainer.py:56-72, 97-101, 134-154
-    perceptual / emotion / MICA terms (:104-131)                -> `extra`: computed by the caller's networks, added by FirstPathLoss with their weights
+    perceptual / emotion / MICA terms (:104-131)                -> `extra`: added by FirstPathLoss with their weights.  The perceptual term is
+                                                                   smirk_amd.VGGPerceptualLoss, the MICA term (pre-training stage, :128-131) is
+                                                                   smirk_amd.MICA.calculate_mica_shape_loss; the emotion term (weight 0.0 in both
+                                                                   shipped configs) is computed by the caller's network
 
 `forward_first_path` is everything up to the loss head, `first_path` adds the head.  Nothing here waits for the host: the terms stay on the device until
 the caller asks for `LossTerms.as_dict()`.
