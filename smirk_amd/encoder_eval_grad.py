@@ -9,7 +9,8 @@ generator (:375).  BatchNorm works from the running statistics, which do not mov
 requires grad, the precision is "f16x3" and the call carries the head.  One torch.autograd.Function per backbone.
 
 Forward — one launch per conv + BatchNorm(eval) + ReLU unit, with the folded (scale, shift) of `MobileNetV3Features._pack()`: `smirk_stem_conv_s2_split16`,
-`smirk_dwconv3x3_split16`, `smirk_conv_igemm_f16x3` / `_f16x1` (act, residual), `smirk_gap_linear_split16`, `smirk_expression_clamps`.  The tape holds the
+`smirk_dwconv3x3_split16`, `smirk_conv_igemm_f16x3` / `_f16x1` (act, residual), `smirk_gap_linear_split16`, `smirk_expression_clamps`, all through the op
+wrappers and the head / clamp frame of encoder_train.py (the train-mode schedule runs the same entries bare, without scale, shift and ReLU).  The tape holds the
 post-activation outputs of the ReLU units only (a ReLU mask is `y > 0`); no pre-BatchNorm tensor exists.  A frozen head has no weight gradient, so no pooled
 vectors are kept: heads of at most 64 outputs (pose, expression) pass no workspace and run pool + Linear as one launch.
 
@@ -30,36 +31,11 @@ Not built: recomputing the expand / depthwise activations inside a fused MBConv 
 import torch
 
 from . import _lib as L
-from .generator_train import TRAIN_ARITH
-from .smirk_generator import _split16
+from .encoder_train import _EncOps, _pw_t, backbone_image, clamp_grad, head_forward, second_backward
 
 
-class _EvalOps:
-    """the C entries of the schedule on the current stream"""
-
-    def __init__(self, device, arith):
-        if arith not in TRAIN_ARITH:
-            raise L.SmirkHipError(f"train_arith must be one of {TRAIN_ARITH}, got {arith!r}")
-        self.lib, self.st, self.dev = L.lib(), L.stream_ptr(), device
-        self.entry = self.lib.smirk_conv_igemm_f16x1 if arith == "f16x1" else self.lib.smirk_conv_igemm_f16x3
-
-    def pointwise(self, x, w, cout, scale=None, shift=None, relu=False, residual=None):
-        B, H, W, cin = x.shape
-        d = L.SmirkConvDesc()
-        d.B, d.H, d.W, d.C0, d.C1, d.Cout = B, H, W, cin, 0, cout
-        d.KH, d.KW, d.stride, d.pad_t, d.pad_l, d.Ho, d.Wo = 1, 1, 1, 0, 0, H, W
-        d.pad_mode, d.act, d.out_mode = L.PAD_ZERO, (L.ACT_RELU if relu else L.ACT_NONE), L.OUT_NHWC
-        out = torch.empty(B, H, W, cout, device=self.dev)
-        P = L.ptr
-        L.check(self.entry(d, P(x), None, P(w), P(scale, allow_none=True), P(shift, allow_none=True), P(residual, allow_none=True), P(out), self.st))
-        return out
-
-    def depthwise(self, x, w9c, scale, shift, stride):
-        B, H, W, C = x.shape
-        out = torch.empty(B, (H + stride - 1) // stride, (W + stride - 1) // stride, C, device=self.dev)
-        P = L.ptr
-        L.check(self.lib.smirk_dwconv3x3_split16(P(x), P(w9c), P(scale), P(shift), P(out), B, H, W, C, stride, 1, self.st))
-        return out
+class _EvalOps(_EncOps):
+    """the shared op wrappers plus the two backward kernels that only the frozen schedule runs"""
 
     def depthwise_backward(self, dy, y_out, s_out, w9c, add, y_in, s_in, shape, stride):
         B, H, W, C = shape
@@ -74,14 +50,6 @@ class _EvalOps:
         dz = torch.empty_like(y)
         L.check(self.lib.smirk_relu_scale_backward_split16(L.ptr(dy), L.ptr(y), L.ptr(s), L.ptr(dz), y.numel() // C, C, self.st))
         return dz
-
-
-def _pw_t(conv, s=None):
-    """weight of the data-gradient 1x1 convolution, split16 [cin][cout]; `s` [cout] = the factor of the BatchNorm(eval) that follows a unit without ReLU"""
-    w = conv.weight.detach().float().reshape(conv.out_channels, conv.in_channels)
-    if s is not None:
-        w = w * s[:, None]
-    return _split16(w.t().contiguous())
 
 
 def _backward_weights(backbone, P):
@@ -109,12 +77,8 @@ class BackboneEvalGradFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, backbone, head, clamp_n_exp, img):
-        img = L.as_f32c(img.detach())
-        if not img.is_cuda:
-            raise L.SmirkHipError("smirk_amd runs on the MI355X HIP device only: got a CPU tensor (no CPU fallback exists)")
-        B, C3, H, W = img.shape
-        if C3 != 3 or H < 32 or W < 32:
-            raise L.SmirkHipError("SmirkEncoder: expected [B, 3, H >= 32, W >= 32] images")
+        img = backbone_image(img)
+        B, _, H, W = img.shape
         ctx.arith = getattr(backbone, "train_arith", "f16x3")
         ops = _EvalOps(img.device, ctx.arith)
         lib, st = ops.lib, ops.st
@@ -135,7 +99,7 @@ class BackboneEvalGradFunction(torch.autograd.Function):
                 pk, tk = P[(si, bi)], T[(si, bi)]
                 if blk.kind == "ds":
                     wdw, s1, b1 = pk["dw"]
-                    y1 = keep(ops.depthwise(x, wdw, s1, b1, blk.stride))
+                    y1 = keep(ops.depthwise(x, wdw, blk.stride, s1, b1, relu=True))
                     w2, s2, b2 = pk["pw"]
                     out = ops.pointwise(y1, w2, blk.conv_pw.out_channels, s2, b2, residual=x if blk.skip else None)
                     tape.append(("ds", blk, (tuple(x.shape), y1, s1, wdw, tk["pw"], relu_in)))
@@ -143,7 +107,7 @@ class BackboneEvalGradFunction(torch.autograd.Function):
                     w1, s1, b1 = pk["pw"]
                     y1 = keep(ops.pointwise(x, w1, blk.conv_pw.out_channels, s1, b1, relu=True))
                     wdw, s2, b2 = pk["dw"]
-                    y2 = keep(ops.depthwise(y1, wdw, s2, b2, blk.stride))
+                    y2 = keep(ops.depthwise(y1, wdw, blk.stride, s2, b2, relu=True))
                     w3, s3, b3 = pk["pwl"]
                     out = ops.pointwise(y2, w3, blk.conv_pwl.out_channels, s3, b3, residual=x if blk.skip else None)
                     tape.append(("ir", blk, (y1, s1, y2, s2, wdw, tk["pw"], tk["pwl"], relu_in)))
@@ -153,38 +117,21 @@ class BackboneEvalGradFunction(torch.autograd.Function):
                     tape.append(("cn", blk, (out, s1, tk["pw"], relu_in)))
                 relu_in = None
                 x = out
-        Bf, hf, wf, Cf = x.shape
-        hw_, hb = head.weight.detach().float().contiguous(), head.bias.detach().float().contiguous()
-        N = hw_.shape[0]
-        pooled = torch.empty(B, Cf, device=img.device) if N > 64 else None       # no pooled vectors kept (the head is frozen): N <= 64 then runs as one launch
-        raw = torch.empty(B, N, device=img.device)
-        L.check(lib.smirk_gap_linear_split16(L.ptr(x), L.ptr(hw_), L.ptr(hb), L.ptr(raw), L.ptr(pooled, allow_none=True), B, hf * wf, Cf, N, st))
-        out = raw
-        if clamp_n_exp >= 0:
-            out = raw.clone()
-            L.check(lib.smirk_expression_clamps(L.ptr(out), B, clamp_n_exp, st))
+        out, hw_, _, raw, dims = head_forward(ops, x, head, clamp_n_exp, keep_pooled=False)      # the head is frozen: no pooled vectors kept
         ctx.tape = tape
-        ctx.headrec = (hw_, raw, clamp_n_exp, (B, hf, wf, Cf, N))
+        ctx.headrec = (hw_, raw, clamp_n_exp, dims)
         ctx.img_shape = (B, H, W)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         if ctx.tape is None:
-            raise RuntimeError("BackboneEvalGradFunction.backward called a second time: the tape of activations is released after the first backward pass "
-                               "(retain_graph=True is not supported by the HIP training path; run the forward again)")
+            raise second_backward("BackboneEvalGradFunction", "activations")
         tape = ctx.tape
         hw_, raw, n_exp, (B, hf, wf, Cf, N) = ctx.headrec
         ops = _EvalOps(raw.device, ctx.arith)
         lib, st = ops.lib, ops.st
-        gout = L.as_f32c(gout)
-        if n_exp >= 0:                                      # torch.clamp / F.relu backward (smirk_encoder.py:104-107): gradient passes inside the range
-            m = torch.ones_like(raw)
-            e, j0, j = raw[:, n_exp:n_exp + 2], raw[:, n_exp + 2:n_exp + 3], raw[:, n_exp + 3:n_exp + 5]
-            m[:, n_exp:n_exp + 2] = ((e >= 0) & (e <= 1)).float()
-            m[:, n_exp + 2:n_exp + 3] = (j0 > 0).float()
-            m[:, n_exp + 3:n_exp + 5] = ((j >= -0.2) & (j <= 0.2)).float()
-            gout = (gout * m).contiguous()
+        gout = clamp_grad(L.as_f32c(gout), raw, n_exp)
         g = torch.empty(B, hf, wf, Cf, device=raw.device)
         L.check(lib.smirk_gap_linear_backward_split16(L.ptr(gout), L.ptr(hw_), None, None, None, L.ptr(g), B, hf * wf, Cf, N, st))
         dimg = None

@@ -13,36 +13,45 @@ One torch.autograd.Function per backbone.  Forward: bare stem / depthwise / poin
 BatchNorm backward, pointwise data gradients on the forward implicit-GEMM kernel with the transposed weight, pointwise weight gradients on the
 split-fp16 x3 weight-gradient kernels (`smirk_conv_wgrad_f32`, csrc/wgrad.hip, default mode 2; the exact-fp32 MFMA kernels are selectable with $SMIRK_WGRAD_F16=0), depthwise / stem / head companions from csrc/train_encoder.hip.  Weight gradients are computed only for parameters that require
 them, the image gradient only if the image requires it.
+
+This module also holds what the frozen eval-mode schedule (encoder_eval_grad.py) shares with this one: the op wrappers (`_EncOps`) and the frame around the
+block loop — image check, pool + Linear + clamps, the clamps' gradient, the second-backward error, the transposed pointwise weight.
 """
 import torch
 
 from . import _lib as L
-from .generator_train import _Ops
+from .generator_train import PackPlan, _Ops
 from .smirk_generator import _split16
 
 
 class _EncOps(_Ops):
+    """generator_train._Ops plus the depthwise entries; the pointwise and depthwise convolutions take the folded BatchNorm (scale, shift) and the ReLU of the
+    frozen eval-mode schedule (encoder_eval_grad.py) as their epilogue, and run bare in the train-mode schedule below"""
+
     def __init__(self, device, arith="f16x3"):
         super().__init__(device, arith=arith)
         self.dw_ws = None
         self.ones, self.zeros = {}, {}
 
-    def pointwise(self, x, w_split, cout, residual=None):
+    def pointwise(self, x, w_split, cout, scale=None, shift=None, relu=False, residual=None):
         B, H, W, _ = x.shape
-        return self.conv(x, None, w_split, B, H, W, cout, k=1, residual=residual)
+        return self.conv(x, None, w_split, B, H, W, cout, k=1, scale=scale, shift=shift, relu=relu, residual=residual)
 
     def pointwise_stats(self, x, w_split, cout):
         """1x1 convolution followed by a BatchNorm: -> (z, partial sums of z or None) (generator_train._Ops.conv_stats)"""
         B, H, W, _ = x.shape
         return self.conv_stats(x, None, w_split, B, H, W, cout, k=1)
 
-    def depthwise(self, x, w9c, stride):
+    def depthwise(self, x, w9c, stride, scale=None, shift=None, relu=False):
+        """3 x 3 depthwise convolution with the epilogue y = act(z * scale + shift); without scale / shift the raw convolution (ones / zeros)"""
         B, H, W, C = x.shape
-        if C not in self.ones:
-            self.ones[C], self.zeros[C] = torch.ones(C, device=self.dev), torch.zeros(C, device=self.dev)
-        out = torch.empty(B, (H + stride - 1) // stride, (W + stride - 1) // stride, C, device=self.dev)
+        if scale is None:
+            if C not in self.ones:
+                self.ones[C], self.zeros[C] = torch.ones(C, device=self.dev), torch.zeros(C, device=self.dev)
+            scale, shift = self.ones[C], self.zeros[C]
+        out = torch.empty(dw_out_shape(x, stride), device=self.dev)
         P = L.ptr
-        L.check(self.lib.smirk_dwconv3x3_split16(P(x), P(w9c), P(self.ones[C]), P(self.zeros[C]), P(out), B, H, W, C, stride, 0, self.st))
+        L.check(self.lib.smirk_dwconv3x3_split16(P(x), P(w9c), P(scale), P(shift), P(out), B, H, W, C, stride, int(relu), self.st))
         return out
 
     def depthwise_stats(self, x, w9c, stride):
@@ -50,7 +59,7 @@ class _EncOps(_Ops):
         if not self.fuse_stats:
             return self.depthwise(x, w9c, stride), None
         B, H, W, C = x.shape
-        out = torch.empty(B, (H + stride - 1) // stride, (W + stride - 1) // stride, C, device=self.dev)
+        out = torch.empty(dw_out_shape(x, stride), device=self.dev)
         part = torch.empty(1024 * C * 2, dtype=torch.float64, device=self.dev)
         rows = L.C.c_int(0)
         rc = self.lib.smirk_dwconv3x3_stats_split16(L.ptr(x), L.ptr(w9c), L.ptr(out), B, H, W, C, stride, L.ptr(part, torch.float64), L.C.byref(rows), self.st)
@@ -75,18 +84,71 @@ class _EncOps(_Ops):
         return dw
 
 
+# ---- the frame around a backbone's block loop, shared with encoder_eval_grad.BackboneEvalGradFunction ---------------------------------------------------------
+def dw_out_shape(x, stride):
+    """output shape of the 3 x 3 depthwise convolution (pad 1) of the NHWC tensor x"""
+    B, H, W, C = x.shape
+    return B, (H + stride - 1) // stride, (W + stride - 1) // stride, C
+
+
+def backbone_image(img):
+    """the image a backbone Function runs on: detached, fp32, contiguous, [B, 3, H >= 32, W >= 32] on the HIP device"""
+    img = L.as_f32c(img.detach())
+    if not img.is_cuda:
+        raise L.SmirkHipError("smirk_amd runs on the MI355X HIP device only: got a CPU tensor (no CPU fallback exists)")
+    B, C3, H, W = img.shape
+    if C3 != 3 or H < 32 or W < 32:
+        raise L.SmirkHipError("SmirkEncoder: expected [B, 3, H >= 32, W >= 32] images")
+    return img
+
+
+def head_forward(ops, x, head, clamp_n_exp, keep_pooled):
+    """global average pool + Linear `head` + the ExpressionEncoder clamps (smirk_encoder.py:104-107) when clamp_n_exp >= 0, on the last feature map x
+    -> (output, head weight as the kernel read it, pooled vectors or None, pre-clamp output, (B, h, w, C, N)).  The pooled vectors are what the head's weight
+    gradient needs; without them (`keep_pooled` False: a frozen head) heads of at most 64 outputs pass no workspace and run pool + Linear as one launch."""
+    B, hf, wf, Cf = x.shape
+    hw_, hb = head.weight.detach().float().contiguous(), head.bias.detach().float().contiguous()
+    N = hw_.shape[0]
+    pooled = torch.empty(B, Cf, device=x.device) if keep_pooled or N > 64 else None
+    raw = torch.empty(B, N, device=x.device)
+    L.check(ops.lib.smirk_gap_linear_split16(L.ptr(x), L.ptr(hw_), L.ptr(hb), L.ptr(raw), L.ptr(pooled, allow_none=True), B, hf * wf, Cf, N, ops.st))
+    out = raw
+    if clamp_n_exp >= 0:
+        out = raw.clone()
+        L.check(ops.lib.smirk_expression_clamps(L.ptr(out), B, clamp_n_exp, ops.st))
+    return out, hw_, pooled, raw, (B, hf, wf, Cf, N)
+
+
+def clamp_grad(gout, raw, n_exp):
+    """torch.clamp / F.relu backward of the ExpressionEncoder clamps (smirk_encoder.py:104-107) on the pre-clamp output `raw`: the gradient passes inside the
+    range, bounds included (eyelids [0, 1], jaw[1:3] [-0.2, 0.2]), and where jaw[0] > 0; n_exp < 0 = no clamps"""
+    if n_exp < 0:
+        return gout
+    m = torch.ones_like(raw)
+    e, j0, j = raw[:, n_exp:n_exp + 2], raw[:, n_exp + 2:n_exp + 3], raw[:, n_exp + 3:n_exp + 5]
+    m[:, n_exp:n_exp + 2] = ((e >= 0) & (e <= 1)).float()
+    m[:, n_exp + 2:n_exp + 3] = (j0 > 0).float()
+    m[:, n_exp + 3:n_exp + 5] = ((j >= -0.2) & (j <= 0.2)).float()
+    return (gout * m).contiguous()
+
+
+def second_backward(function, held):
+    """the error of a backward pass over a tape that the first one released"""
+    return RuntimeError(f"{function}.backward called a second time: the tape of {held} is released after the first backward pass "
+                        "(retain_graph=True is not supported by the HIP training path; run the forward again)")
+
+
 def _pw(conv):
     """nn.Conv2d(cin, cout, 1) weight -> split16 [cout][cin]   (test helper; the step itself uses _EncOps.pack: both images in one launch)"""
     return _split16(conv.weight.detach().float().reshape(conv.out_channels, conv.in_channels).contiguous())
 
 
-def _pw_t(conv):
-    """transposed: the weight of the data-gradient 1x1 convolution, split16 [cin][cout]"""
-    return _split16(conv.weight.detach().float().reshape(conv.out_channels, conv.in_channels).t().contiguous())
-
-
-def _dw(conv):
-    return conv.weight.detach().float().reshape(conv.out_channels, 9).t().contiguous()                  # [9][C]
+def _pw_t(conv, s=None):
+    """weight of the data-gradient 1x1 convolution, split16 [cin][cout]; `s` [cout] = the factor of the BatchNorm(eval) that follows a unit without ReLU"""
+    w = conv.weight.detach().float().reshape(conv.out_channels, conv.in_channels)
+    if s is not None:
+        w = w * s[:, None]
+    return _split16(w.t().contiguous())
 
 
 class BackboneTrainFunction(torch.autograd.Function):
@@ -95,16 +157,11 @@ class BackboneTrainFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, backbone, head, clamp_n_exp, img, *params):
-        img = L.as_f32c(img.detach())
-        if not img.is_cuda:
-            raise L.SmirkHipError("smirk_amd runs on the MI355X HIP device only: got a CPU tensor (no CPU fallback exists)")
-        B, C3, H, W = img.shape
-        if C3 != 3 or H < 32 or W < 32:
-            raise L.SmirkHipError("SmirkEncoder: expected [B, 3, H >= 32, W >= 32] images")
+        img = backbone_image(img)
+        B, _, H, W = img.shape
         ctx.arith = getattr(backbone, "train_arith", "f16x3")            # generator_train.TRAIN_ARITH: "f16x1" = pointwise convs, their data and weight gradients on one MFMA
         ops = _EncOps(img.device, arith=ctx.arith)
         lib, st = ops.lib, ops.st
-        from .generator_train import PackPlan
         plan = getattr(backbone, "_pack_plan", None)                      # every pointwise weight of the backbone: one packing launch per forward
         if plan is None or not plan.valid_for(params):
             plan = PackPlan()
@@ -146,29 +203,19 @@ class BackboneTrainFunction(torch.autograd.Function):
                     out, m1, i1 = ops.bn_forward(z1, blk.bn1, True, stats=s1)
                     tape.append(("cn", blk, (x, z1, m1, i1, wt)))
                 x = out
-        Bf, hf, wf, Cf = x.shape
-        hw_, hb = head.weight.detach().float().contiguous(), head.bias.detach().float().contiguous()
-        N = hw_.shape[0]
-        pooled = torch.empty(B, Cf, device=img.device)
-        raw = torch.empty(B, N, device=img.device)
-        L.check(lib.smirk_gap_linear_split16(L.ptr(x), L.ptr(hw_), L.ptr(hb), L.ptr(raw), L.ptr(pooled), B, hf * wf, Cf, N, st))
-        out = raw
-        if clamp_n_exp >= 0:
-            out = raw.clone()
-            L.check(lib.smirk_expression_clamps(L.ptr(out), B, clamp_n_exp, st))
+        out, hw_, pooled, raw, dims = head_forward(ops, x, head, clamp_n_exp, keep_pooled=True)
         if not plan.sealed:
             plan.seal(params, img.device)
         ctx.plan, (ctx.plan_generation, ctx.plan_versions) = plan, plan.stamp(params)       # see PackPlan.check_tape
         ctx.backbone, ctx.head, ctx.tape = backbone, head, tape
-        ctx.headrec = (hw_, pooled, raw, clamp_n_exp, (B, hf, wf, Cf, N))
+        ctx.headrec = (hw_, pooled, raw, clamp_n_exp, dims)
         ctx.img_shape = (B, H, W)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         if ctx.tape is None:
-            raise RuntimeError("BackboneTrainFunction.backward called a second time: the tape of raw convolution outputs is released after the first "
-                               "backward pass (retain_graph=True is not supported by the HIP training path; run the forward again)")
+            raise second_backward("BackboneTrainFunction", "raw convolution outputs")
         backbone, head, tape = ctx.backbone, ctx.head, ctx.tape
         ctx.plan.check_tape(ctx.plan_generation, ctx.plan_versions)
         hw_, pooled, raw, n_exp, (B, hf, wf, Cf, N) = ctx.headrec
@@ -176,14 +223,7 @@ class BackboneTrainFunction(torch.autograd.Function):
         lib, st = ops.lib, ops.st
         grads = {}
         need = lambda p: p.requires_grad
-        gout = L.as_f32c(gout)
-        if n_exp >= 0:                                      # torch.clamp / F.relu backward (smirk_encoder.py:104-107): gradient passes inside the range
-            m = torch.ones_like(raw)
-            e, j0, j = raw[:, n_exp:n_exp + 2], raw[:, n_exp + 2:n_exp + 3], raw[:, n_exp + 3:n_exp + 5]
-            m[:, n_exp:n_exp + 2] = ((e >= 0) & (e <= 1)).float()
-            m[:, n_exp + 2:n_exp + 3] = (j0 > 0).float()
-            m[:, n_exp + 3:n_exp + 5] = ((j >= -0.2) & (j <= 0.2)).float()
-            gout = (gout * m).contiguous()
+        gout = clamp_grad(L.as_f32c(gout), raw, n_exp)
         want_head = need(head.weight) or need(head.bias)
         dwh = torch.empty(N, Cf, device=raw.device) if want_head else None
         dbh = torch.empty(N, device=raw.device) if want_head else None

@@ -10,8 +10,11 @@ Here the whole network is ONE torch.autograd.Function.  Forward: raw convolution
 swapped, weight gradients on `smirk_conv_wgrad_f32` (split-fp16 x3 MFMA with LDS transpose reads; exact fp32 MFMA selectable), max-pool / reflection-pad / ConvTranspose2d / sigmoid companions
 (csrc/train.hip, csrc/wgrad.hip).  Arithmetic: split-fp16 x3 MFMA for the convolutions and their data gradients (fp32-class, like inference), fp32 / fp64 for
 statistics and weight gradients — tighter than the bf16 autocast BASELINE config 5 names.  The layer schedule lives in Python for now (a training
-step is ~25 ms of GPU time at B = 64; the host is not yet the limiter).
+step is ~25 ms of GPU time at B = 64; the host is not yet the limiter): `_Ops` wraps the C entries for this schedule and for the encoder's two
+(encoder_train.py, encoder_eval_grad.py); every convolution descriptor comes from _lib.conv_desc and every convolution launch from _lib.conv_launch.
 """
+import os
+
 import torch
 
 from . import _lib as L
@@ -62,7 +65,9 @@ def _grad_like(weight):
 
 
 class _Ops:
-    """thin stateful wrapper over the C entries: one reduction workspace, the launch stream, and conv descriptors"""
+    """thin stateful wrapper over the C entries, shared by every training schedule (encoder_train._EncOps and encoder_eval_grad._EvalOps build on it): the
+    launch stream, the convolution entry `arith` selects (checked against TRAIN_ARITH here and nowhere else), one reduction workspace.  Convolutions go
+    through _lib.conv_desc / _lib.conv_launch."""
 
     def __init__(self, device, eval_bn=False, arith="f16x3"):
         self.lib, self.st, self.dev = L.lib(), L.stream_ptr(), device
@@ -70,26 +75,25 @@ class _Ops:
         if arith not in TRAIN_ARITH:
             raise L.SmirkHipError(f"train_arith must be one of {TRAIN_ARITH}, got {arith!r}")
         self.x1 = arith == "f16x1"                       # one MFMA per product block (hi halves only): BASELINE config 5's 16-bit class
+        self.entry = self.lib.smirk_conv_igemm_f16x1 if self.x1 else self.lib.smirk_conv_igemm_f16x3
         self.plan = None
-        import os
         self.fuse_stats = not os.environ.get("SMIRK_BN_STATS_UNFUSED")       # A/B switch for tests: BatchNorm statistics by a pass over the stored tensor
         self.rm_saved = {}                                # eval-mode BatchNorm: id(bn) -> running_mean as the forward saw it
-        self.red_ws = torch.empty(self.lib.smirk_train_reduce_workspace_bytes(1024), dtype=torch.uint8, device=device)
-        self.wg_ws = None
+        self._red_ws = self.wg_ws = None
+
+    @property
+    def red_ws(self):
+        """the reduction scratch of the BatchNorm / column-sum entries, allocated by the first of them (the frozen eval path runs none)"""
+        if self._red_ws is None:
+            self._red_ws = torch.empty(self.lib.smirk_train_reduce_workspace_bytes(1024), dtype=torch.uint8, device=self.dev)
+        return self._red_ws
 
     def conv_stats(self, x0, x1, w, B, H, W, cout, k=3, reflect=False):
         """the raw convolution whose BatchNorm follows: -> (z, (partials, rows) or None).  The kernel leaves per-tile partial sums (sum z, sum z^2) of its output
         from the MFMA accumulators where the kernel family serving the shape can (smirk_conv_igemm_stats_split16); `None` = reduce the stored tensor instead."""
         if self.eval_bn or not self.fuse_stats:
             return self.conv(x0, x1, w, B, H, W, cout, k=k, reflect=reflect), None
-        d = L.SmirkConvDesc()
-        d.B, d.H, d.W = B, H, W
-        d.C0, d.C1 = x0.shape[-1], (x1.shape[-1] if x1 is not None else 0)
-        d.Cout, d.KH, d.KW, d.stride = cout, k, k, 1
-        d.pad_t = d.pad_l = (k - 1) // 2
-        d.Ho, d.Wo = H, W
-        d.pad_mode = L.PAD_REFLECT if reflect else L.PAD_ZERO
-        d.act, d.out_mode = L.ACT_NONE, L.OUT_NHWC
+        d = L.conv_desc(B, H, W, x0.shape[-1], cout, k, c1=x1.shape[-1] if x1 is not None else 0, reflect=reflect)
         out = torch.empty((B, H, W, cout), device=self.dev)
         part = torch.empty((self.lib.smirk_conv_stats_rows_max(d), cout, 2), device=self.dev)
         rows = L.C.c_int(0)
@@ -97,21 +101,10 @@ class _Ops:
         L.check(self.lib.smirk_conv_igemm_stats_split16(d, P(x0), P(x1, allow_none=True), P(w), P(out), P(part), L.C.byref(rows), int(self.x1), self.st))
         return out, ((part, rows.value) if rows.value > 0 else None)
 
-    def conv(self, x0, x1, w, B, H, W, cout, k=3, reflect=False, pad=None, out_hw=None, convt=False, shift=None, residual=None):
-        d = L.SmirkConvDesc()
-        d.B, d.H, d.W = B, H, W
-        d.C0, d.C1 = x0.shape[-1], (x1.shape[-1] if x1 is not None else 0)
-        d.Cout, d.KH, d.KW, d.stride = cout, k, k, 1
-        d.pad_t = d.pad_l = (k - 1) // 2 if pad is None else pad
-        d.Ho, d.Wo = (H, W) if out_hw is None else out_hw
-        d.pad_mode = L.PAD_REFLECT if reflect else L.PAD_ZERO
-        d.act = L.ACT_NONE
-        d.out_mode = L.OUT_CONVT2X2 if convt else L.OUT_NHWC
-        out = torch.empty((B, 2 * H, 2 * W, cout) if convt else (B, d.Ho, d.Wo, cout), device=self.dev)
-        P = L.ptr
-        entry = self.lib.smirk_conv_igemm_f16x1 if self.x1 else self.lib.smirk_conv_igemm_f16x3
-        L.check(entry(d, P(x0), P(x1, allow_none=True), P(w), None, P(shift, allow_none=True), P(residual, allow_none=True), P(out), self.st))
-        return out
+    def conv(self, x0, x1, w, B, H, W, cout, k=3, reflect=False, pad=None, out_hw=None, convt=False, scale=None, shift=None, relu=False, residual=None):
+        """stride-1 convolution of x0 (+ x1, concatenated along the channels) on the entry `arith` selects; scale / shift / relu / residual are its epilogue"""
+        d = L.conv_desc(B, H, W, x0.shape[-1], cout, k, c1=x1.shape[-1] if x1 is not None else 0, pad=pad, out_hw=out_hw, reflect=reflect, relu=relu, convt=convt)
+        return L.conv_launch(self.entry, d, self.st, x0, w, x1, scale, shift, residual)
 
     def pack(self, weight, cin_off=0, cin=None, cin_pad=None, fwd=True, dgrad=True):
         """nn.Conv2d weight (fp32 parameter) -> (forward weight split16 [Cout][T*cin_pad] or None, data-gradient weight split16 [cin_pad][T*Cout] or None).

@@ -185,7 +185,7 @@ class MICA(nn.Module):
     def _operands(self, dev):
         if self._tensors is None:
             self._tensors = [t for n, t in list(self.named_parameters()) + list(self.named_buffers()) if not n.endswith("num_batches_tracked")]
-        key = tuple((t.data_ptr(), t._version) for t in self._tensors)
+        key = L.version_key(self._tensors)
         if self._packed is not None and self._packed[0] == key:
             return self._packed[1]
         for t in self._tensors:
@@ -235,16 +235,10 @@ class MICA(nn.Module):
         B, _, H, W = img.shape
         x = torch.empty(B, H, W, 8, device=dev)
         L.check(lib.smirk_mica_prepare_split16(P(img), P(x), B, H, W, st))
-        d = L.SmirkConvDesc()
-        d.B, d.C1, d.pad_mode, d.act, d.out_mode = B, 0, L.PAD_ZERO, L.ACT_NONE, L.OUT_NHWC
 
         def conv(src, op, k, stride, residual=None):
             _, h, w, c = src.shape
-            ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
-            d.H, d.W, d.C0, d.Cout, d.KH, d.KW, d.stride, d.pad_t, d.pad_l, d.Ho, d.Wo = h, w, c, op[1].numel(), k, k, stride, k // 2, k // 2, ho, wo
-            out = torch.empty(B, ho, wo, op[1].numel(), device=dev)
-            L.check(lib.smirk_conv_igemm_f16x3(d, P(src), None, P(op[0]), P(op[1]), P(op[2]), P(residual, allow_none=True), P(out), st))
-            return out
+            return L.conv_launch(lib.smirk_conv_igemm_f16x3, L.conv_desc(B, h, w, c, op[1].numel(), k, stride=stride), st, src, op[0], None, op[1], op[2], residual)
 
         def stream(src, scale, shift, slope, dst):
             L.check(lib.smirk_mica_affine_prelu_split16(P(src), P(scale, allow_none=True), P(shift, allow_none=True), P(slope, allow_none=True), P(dst),

@@ -111,7 +111,7 @@ class MobileNetV3Features(nn.Module):
         return super().train(mode)
 
     def _key(self):
-        return (PRECISION,) + tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
+        return (PRECISION,) + L.version_key(list(self.parameters()) + list(self.buffers()))
 
     @staticmethod
     def _affine(bn):
@@ -152,7 +152,7 @@ class MobileNetV3Features(nn.Module):
     def _weights(self, head=None, clamp_n_exp=-1):
         """SmirkBackboneWeights for smirk_backbone_forward (host struct of device pointers; cached per parameter version and head)."""
         P = self._pack()
-        hkey = None if head is None else (head.weight.data_ptr(), head.weight._version, head.bias.data_ptr(), head.bias._version)
+        hkey = None if head is None else L.version_key((head.weight, head.bias))
         ck = (self._packed_key, hkey, clamp_n_exp)
         hit = self._wcache.get("w")
         if hit is not None and hit[0] == ck:

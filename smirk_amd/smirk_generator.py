@@ -111,7 +111,7 @@ class SmirkGenerator(nn.Module):
 
     # ---- weight packing (device-side, cached until a parameter changes) ---------------------------------------------------
     def _key(self):
-        return (self.precision,) + tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
+        return (self.precision,) + L.version_key(list(self.parameters()) + list(self.buffers()))
 
     def _pack(self):
         key = self._key()

@@ -79,17 +79,12 @@ class _VGGLoss(torch.autograd.Function):
         relu_x, tap_full, cur, h, w = [], [], xin, H, W
         if trace is not None:
             trace["relu_x"], trace["tap_y"] = [], []
-        d = L.SmirkConvDesc()
-        d.B, d.KH, d.KW, d.stride, d.pad_t, d.pad_l = 2 * B, 3, 3, 1, 1, 1
-        d.C1, d.pad_mode, d.act, d.out_mode = 0, L.PAD_ZERO, L.ACT_RELU, L.OUT_NHWC
         for k, cout in enumerate(CHANNELS):
             if k in POOL_BEFORE:
                 pooled = torch.empty(2 * B, h // 2, w // 2, cur.shape[-1], device=dev)
                 L.check(lib.smirk_maxpool2x2_split16(P(cur), P(pooled), 2 * B, h, w, cur.shape[-1], st))
                 cur, h, w = pooled, h // 2, w // 2
-            d.H, d.W, d.Ho, d.Wo, d.C0, d.Cout = h, w, h, w, cur.shape[-1], cout
-            out = torch.empty(2 * B, h, w, cout, device=dev)
-            L.check(lib.smirk_conv_igemm_f16x3(d, P(cur), None, P(wf[k]), None, P(bias[k]), None, P(out), st))
+            out = L.conv_launch(lib.smirk_conv_igemm_f16x3, L.conv_desc(2 * B, h, w, cur.shape[-1], cout, 3, relu=True), st, cur, wf[k], shift=bias[k])
             if k in TAPS:
                 L.check(lib.smirk_vgg_l1_partials_split16(P(out), cout, TAPS.index(k), half, len(TAPS), wsp, ws.numel(), st))
             if keep:                                                     # the x rows of every ReLU output; of the y rows the four tap features only
@@ -125,9 +120,6 @@ class _VGGLoss(torch.autograd.Function):
         lib, st, dev = L.lib(), L.stream_ptr(), relu_x[0].device
         P = L.ptr
         g = L.as_f32c(g_total.detach())
-        d = L.SmirkConvDesc()
-        d.B, d.KH, d.KW, d.stride, d.pad_t, d.pad_l = B, 3, 3, 1, 1, 1
-        d.C1, d.pad_mode, d.act, d.out_mode = 0, L.PAD_ZERO, L.ACT_NONE, L.OUT_NHWC
         grad = None
         for k in range(len(CHANNELS) - 1, -1, -1):
             fx = relu_x[k]
@@ -136,9 +128,7 @@ class _VGGLoss(torch.autograd.Function):
             dz = torch.empty_like(fx)
             L.check(lib.smirk_vgg_relu_tap_backward_split16(P(fx), P(fy, allow_none=True), P(grad, allow_none=True), P(g), P(dz), fx.numel(), c, scale, st))
             cin = wd[k].shape[0]
-            d.H, d.W, d.Ho, d.Wo, d.C0, d.Cout = h, w, h, w, c, cin
-            grad = torch.empty(B, h, w, cin, device=dev)
-            L.check(lib.smirk_conv_igemm_f16x3(d, P(dz), None, P(wd[k]), None, None, None, P(grad), st))
+            grad = L.conv_launch(lib.smirk_conv_igemm_f16x3, L.conv_desc(B, h, w, c, cin, 3), st, dz, wd[k])
             if k in POOL_BEFORE:
                 up = torch.empty_like(relu_x[k - 1])
                 L.check(lib.smirk_maxpool2x2_backward_split16(P(relu_x[k - 1]), P(grad), None, P(up), B, 2 * h, 2 * w, cin, st))

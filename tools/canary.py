@@ -38,17 +38,13 @@ def main():
             lib.smirk_f32_to_split16(L.ptr(torch.randn(B, H, H, cin1, device="cuda")), L.ptr(xs1), xs1.numel(), None)
         sc, sh = torch.ones(cout, device="cuda"), torch.zeros(cout, device="cuda")
         out = torch.empty((B, 2 * H, 2 * H, cout) if convt else (B, H, H, cout), device="cuda")
-        d = L.SmirkConvDesc()
-        d.B, d.H, d.W, d.C0, d.C1, d.Cout, d.KH, d.KW, d.stride = B, H, H, cin0, cin1, cout, k, k, 1
-        d.pad_t = d.pad_l = (k - 1) // 2
-        d.Ho, d.Wo, d.pad_mode, d.act = H, H, L.PAD_ZERO, L.ACT_RELU
-        d.out_mode = L.OUT_CONVT2X2 if convt else L.OUT_NHWC
+        d = L.conv_desc(B, H, H, cin0, cout, k, c1=cin1, relu=True, convt=convt)
         torch.cuda.synchronize()
 
         def run(reps):
             st = L.stream_ptr()
             for _ in range(reps):
-                L.check(lib.smirk_conv_igemm_f16x3(d, L.ptr(xs0), L.ptr(xs1, allow_none=True), L.ptr(ws), L.ptr(sc), L.ptr(sh), None, L.ptr(out), st))
+                L.conv_launch(lib.smirk_conv_igemm_f16x3, d, st, xs0, ws, xs1, sc, sh, out=out)
         return run
 
     a_mat = torch.randn(8192, 8192, device="cuda")

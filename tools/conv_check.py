@@ -23,16 +23,10 @@ def run(B, H, C0, C1, Cout):
     K = 9 * (C0 + C1)
     w = (torch.randn(Cout, K, generator=g) * 0.05).to(dev)
     sc, sh = (torch.rand(Cout, generator=g) + .5).to(dev), torch.randn(Cout, generator=g).to(dev)
-    d = L.SmirkConvDesc()
-    d.B, d.H, d.W, d.C0, d.C1, d.Cout, d.KH, d.KW, d.stride = B, H, H, C0, C1, Cout, 3, 3, 1
-    d.pad_t = d.pad_l = 1
-    d.Ho, d.Wo, d.pad_mode, d.act, d.out_mode = H, H, L.PAD_ZERO, L.ACT_RELU, L.OUT_NHWC
-    P = L.ptr
-    o32 = torch.empty(B, H, H, Cout, device=dev)
-    L.check(lib.smirk_conv_igemm_f32(d, P(x0), P(x1, allow_none=True), P(w), P(sc), P(sh), None, P(o32), L.stream_ptr()))
-    os_ = torch.empty(B, H, H, Cout, device=dev)
+    d = L.conv_desc(B, H, H, C0, Cout, 3, c1=C1, relu=True)
+    o32 = L.conv_launch(lib.smirk_conv_igemm_f32, d, L.stream_ptr(), x0, w, x1, sc, sh)
     s0, s1, ws = to_split(x0), (to_split(x1) if C1 else None), _split16(w)      # keep references alive across the async launch
-    L.check(lib.smirk_conv_igemm_f16x3(d, P(s0), P(s1, allow_none=True), P(ws), P(sc), P(sh), None, P(os_), L.stream_ptr()))
+    os_ = L.conv_launch(lib.smirk_conv_igemm_f16x3, d, L.stream_ptr(), s0, ws, s1, sc, sh)
     torch.cuda.synchronize()
     a, b = o32, split16_to_float(os_)
     err = (a - b).abs()

@@ -23,16 +23,9 @@ def run(B, H, C0, C1, Cout, k, convt, reflect, iters, split=False):
     w = torch.randn(n, K, device=dev) * 0.05
     sc, sh = torch.rand(Cout, device=dev) + .5, torch.randn(Cout, device=dev)
     out = torch.empty((B, 2 * H, 2 * H, Cout) if convt else (B, H, H, Cout), device=dev)
-    d = L.SmirkConvDesc()
-    d.B, d.H, d.W, d.C0, d.C1, d.Cout, d.KH, d.KW, d.stride = B, H, H, C0, C1, Cout, k, k, 1
-    d.pad_t = d.pad_l = (k - 1) // 2
-    d.Ho, d.Wo = H, H
-    d.pad_mode = L.PAD_REFLECT if reflect else L.PAD_ZERO
-    d.act = L.ACT_RELU
-    d.out_mode = L.OUT_CONVT2X2 if convt else L.OUT_NHWC
-    P = L.ptr
+    d = L.conv_desc(B, H, H, C0, Cout, k, c1=C1, reflect=bool(reflect), relu=True, convt=bool(convt))
     fn = lib.smirk_conv_igemm_f16x3 if split else lib.smirk_conv_igemm_f32
-    call = lambda: L.check(fn(d, P(x0), P(x1, allow_none=True), P(w), P(sc), P(sh), None, P(out), L.stream_ptr()))
+    call = lambda: L.conv_launch(fn, d, L.stream_ptr(), x0, w, x1, sc, sh, out=out)
     call(); torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()

@@ -6,15 +6,9 @@ from smirk_amd.smirk_generator import _split16
 lib = L.lib()
 dev = torch.device("cuda")
 def conv(B, H, C0, C1, Cout, reflect, x0, x1, w, sc, sh, out):
-    d = L.SmirkConvDesc()
     convt = reflect == 2
-    k = 1 if convt else 3
-    d.B, d.H, d.W, d.C0, d.C1, d.Cout, d.KH, d.KW, d.stride = B, H, H, C0, C1, Cout, k, k, 1
-    d.pad_t = d.pad_l = (k - 1) // 2; d.Ho, d.Wo = H, H
-    d.pad_mode = L.PAD_REFLECT if reflect == 1 else L.PAD_ZERO
-    d.act, d.out_mode = (L.ACT_NONE if convt else L.ACT_RELU), (L.OUT_CONVT2X2 if convt else L.OUT_NHWC)
-    P = L.ptr
-    L.check(lib.smirk_conv_igemm_f16x3(d, P(x0), P(x1, allow_none=True), P(w), P(sc), P(sh), None, P(out), L.stream_ptr()))
+    d = L.conv_desc(B, H, H, C0, Cout, 1 if convt else 3, c1=C1, reflect=reflect == 1, relu=not convt, convt=convt)
+    L.conv_launch(lib.smirk_conv_igemm_f16x3, d, L.stream_ptr(), x0, w, x1, sc, sh, out=out)
 from smirk_amd import SmirkGenerator
 g2 = SmirkGenerator(6, 3, 32, 5).cuda().eval(); big = torch.rand(64, 6, 224, 224, device=dev)
 noise_s = torch.cuda.Stream()
