@@ -127,6 +127,13 @@ static inline void conv_prof_next(const char* name, const ConvArgs& a) {
 bool smirk_conv3x3_ring64_eligible(const SmirkConvDesc* d, bool has_residual);
 int smirk_conv3x3_ring64_launch(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale, const float* shift, void* out,
                                 void* pooled, hipStream_t st, float* stats = nullptr, int* stats_rows = nullptr);
+// conv_upcat.hip: a decoder level's ConvTranspose2d(2c -> c, k2 s2) composed into the 3x3 convolution over cat(up, skip) (c = 32 / 64, split-fp16 only); the
+// composed weights and the 16 shift rows are rebuilt per call into caller-provided workspace
+bool smirk_conv3x3_upcat_eligible(int c, int H, int W);
+size_t smirk_conv3x3_upcat_weff_bytes(int c);
+size_t smirk_conv3x3_upcat_shift_bytes(int c);
+int smirk_conv3x3_upcat_launch(int c, const void* d, const void* e, const SmirkConvLayer* up, const SmirkConvLayer* conv, void* out, int B, int H, int W,
+                               void* weff, void* shift4, hipStream_t st);
 // conv_patch.hip: persistent halo-patch kernel for the large-image / few-channel 3x3 layers (split-fp16 only)
 bool smirk_conv3x3_patch_eligible(const SmirkConvDesc* d, bool has_residual);
 int smirk_conv3x3_patch_launch(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale,

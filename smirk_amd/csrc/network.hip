@@ -18,7 +18,7 @@
 #include <unistd.h>
 #include <stdlib.h>
 
-#include "common.h"
+#include "conv_common.h"
 
 namespace {
 
@@ -49,6 +49,8 @@ struct GenPlan {
     void* x;         // packed network input [B][H][W][cin_pad]
     void* e[4];      // skip tensors
     Rot rot;
+    void* upcat_w[2];   // decoder levels 1 / 2 (index = l): composed ConvTranspose x conv weights and shift rows (conv_upcat.hip), rebuilt by every forward
+    void* upcat_s[2];
     size_t total;
 };
 
@@ -60,6 +62,11 @@ GenPlan plan_generator(const SmirkGeneratorWeights* w, int B, int H, int W, void
     for (int l = 0; l < 4; ++l) p.e[l] = a.take(act_bytes(B, H >> l, W >> l, f << l));
     const size_t big = act_bytes(B, H, W, f);                       // the largest temporary: enc1conv1 out, up1, dec1conv1 out
     for (int i = 0; i < 3; ++i) p.rot.slot[i] = a.take(big);
+    for (int l = 0; l < 2; ++l) {
+        const bool on = w->precision == SMIRK_PRECISION_F16X3 && f == 32;
+        p.upcat_w[l] = on ? a.take(smirk_conv3x3_upcat_weff_bytes(f << l)) : nullptr;
+        p.upcat_s[l] = on ? a.take(smirk_conv3x3_upcat_shift_bytes(f << l)) : nullptr;
+    }
     p.total = smirk_align_up(a.off, 256);
     return p;
 }
@@ -323,10 +330,17 @@ extern "C" int smirk_generator_forward(const SmirkGeneratorWeights* w, const flo
     // ---- decoder4..1 (smirk_generator.py:65-75): ConvTranspose2d k2 s2, cat with the skip (two-source conv), double conv -------------------
     for (int l = L0 - 1; l >= 0; --l) {                              // decoder levels above the section, whole batch
         const int h = H >> l, wd = W >> l, c = f << l;              // output resolution of this level
-        void* up = p.rot.pick(dcur, nullptr);
-        TRY(conv_call(split, desc1x1(B, h / 2, wd / 2, 2 * c, c, false, true), dcur, nullptr, w->up[3 - l], nullptr, up, stream));
-        void* t1 = p.rot.pick(up, nullptr);
-        TRY(conv_call(split, desc3x3(B, h, wd, c, c, c, false, true), up, p.e[l], w->dec[3 - l][0], nullptr, t1, stream));
+        void* t1;
+        if (l < 2 && split && f == 32 && smirk_conv3x3_upcat_eligible(c, h, wd)) {
+            // levels 1 / 2: the ConvTranspose composed into the convolution that reads it (conv_upcat.hip) — no `up` tensor; $SMIRK_CONV_RING=0 restores the two launches
+            t1 = p.rot.pick(dcur, nullptr);
+            TRY(smirk_conv3x3_upcat_launch(c, dcur, p.e[l], &w->up[3 - l], &w->dec[3 - l][0], t1, B, h, wd, p.upcat_w[l], p.upcat_s[l], (hipStream_t)stream));
+        } else {
+            void* up = p.rot.pick(dcur, nullptr);
+            TRY(conv_call(split, desc1x1(B, h / 2, wd / 2, 2 * c, c, false, true), dcur, nullptr, w->up[3 - l], nullptr, up, stream));
+            t1 = p.rot.pick(up, nullptr);
+            TRY(conv_call(split, desc3x3(B, h, wd, c, c, c, false, true), up, p.e[l], w->dec[3 - l][0], nullptr, t1, stream));
+        }
         if (l == 0 && split && !taps && f == 32 && H >= 64) {
             // network tail in one launch: dec1conv2 + BN + ReLU + final 1x1 conv + sigmoid (dec1 never reaches HBM)
             SmirkConvDesc d = desc3x3(B, h, wd, c, 0, c, false, true);

@@ -7,7 +7,9 @@
 //                                   included): 1, every eligible geometry on conv_halo_kernel
 // SMIRK_IGEMM_PP                    "0": 0, conv_pp_kernel off; "a...": 2, conv_pp_kernel for every eligible shape         1 (<= 16x16     tests/test_conv_gpu.py
 //                                   (not only images of at most 256 pixels); anything else: 1                             images)
-// SMIRK_CONV_RING                   "0": 0, the 64-output-channel ring kernels off (round-3 kernels); anything else: 1     1               tests/test_conv_gpu.py
+// SMIRK_CONV_RING                   "0": 0, the 64-output-channel ring kernels off (round-3 kernels) and the generator's   1               tests/test_conv_gpu.py,
+//                                   decoder levels 1 / 2 back on their two launches (ConvTranspose, then the convolution                  tests/test_upcat_gpu.py
+//                                   over cat(up, skip)) instead of conv3x3_upcat_kernel; anything else: 1
 // SMIRK_DISABLE_PATCH_KERNEL        set (any value, "0" too): 1, neither the patch nor the ring convolution kernels        0               (integrators)
 // SMIRK_DISABLE_ENC1_FUSED          set (any value): 1, smirk_enc1_fused_supported answers 0                              0               tests/test_conv_gpu.py
 // The next four reach backbone_plan (network.hip) as one struct of values; its priority table says what each takes away:
