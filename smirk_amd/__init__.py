@@ -52,6 +52,7 @@ from .losses import FirstPathLoss, LossTerms, weighted_loss  # noqa: F401  (smir
 from . import first_path, losses  # noqa: F401  (smirk_trainer.py:34-154 over the modules)
 from .vgg_loss import VGGPerceptualLoss  # noqa: E402,F401  (smirk_trainer.py:104: the first path's perceptual term; drop-in for src.losses.VGGPerceptualLoss)
 from .mica import MICA, MappingNetwork  # noqa: E402,F401  (smirk_trainer.py:128-131: the pre-training stage's shape term; drop-in for src.models.MICA.mica)
+from .expression_loss import ExpressionLoss  # noqa: E402,F401  (smirk_trainer.py:108-119: the first path's emotion term; drop-in for src.losses.ExpressionLoss)
 
 
 def check_numerics():
@@ -63,4 +64,4 @@ def check_numerics():
 
 
 __all__ = ["FLAME", "Renderer", "SmirkEncoder", "SmirkGenerator", "SmirkHipError", "lib", "masking", "VideoPipeline", "check_numerics", "TemplateBank", "augment_flame_params",
-           "load_templates", "FirstPathLoss", "LossTerms", "weighted_loss", "losses", "first_path", "VGGPerceptualLoss", "MICA", "MappingNetwork"]
+           "load_templates", "FirstPathLoss", "LossTerms", "weighted_loss", "losses", "first_path", "VGGPerceptualLoss", "MICA", "MappingNetwork", "ExpressionLoss"]

@@ -229,6 +229,22 @@ MICA_SIGS = {
 }
 MICA_EXPORTS = tuple(MICA_SIGS)
 
+# The extension table of include/smirk_emotion.h (the frozen emotion network of the first path): again the same shared object and a version of its own.
+EMOTION_ABI_VERSION = 1
+EMOTION_STEM_COUT, EMOTION_STEM_K, EMOTION_STEM_KPAD = 64, 147, 160   # include/smirk_emotion.h SMIRK_EMOTION_STEM_COUT, _STEM_K, _STEM_KPAD
+EMOTION_METRICS = {"l2": 0, "l1": 1, "cos": 2}                        # SMIRK_EMOTION_L2, _L1, _COS
+EMOTION_SIGS = {
+    "smirk_emotion_abi_version": (_i, []),
+    "smirk_emotion_stem_split16": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "smirk_emotion_stem_dgrad_split16": (_i, [_p, _p, _p, C.c_float, _p, _i, _i, _i, _p]),
+    "smirk_emotion_maxpool_split16": (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    "smirk_emotion_maxpool_backward_split16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "smirk_emotion_dilate2_split16": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "smirk_emotion_head_forward_split16": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "smirk_emotion_head_backward_split16": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, C.c_float, _p]),
+}
+EMOTION_EXPORTS = tuple(EMOTION_SIGS)
+
 _LIB = None
 
 
@@ -244,11 +260,11 @@ def lib():
             raise SmirkHipError(f"{LIB_PATH} not found: build it with `python -m smirk_amd.build` "
                                 "(smirk_amd has no CPU / eager fallback)")
         L = C.CDLL(LIB_PATH)
-        for table in (_SIGS, MICA_SIGS):
+        for table in (_SIGS, MICA_SIGS, EMOTION_SIGS):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)       # AttributeError => header / library mismatch
                 fn.restype, fn.argtypes = res, args
-        if L.smirk_abi_version() != ABI_VERSION or L.smirk_mica_abi_version() != MICA_ABI_VERSION:
+        if L.smirk_abi_version() != ABI_VERSION or L.smirk_mica_abi_version() != MICA_ABI_VERSION or L.smirk_emotion_abi_version() != EMOTION_ABI_VERSION:
             raise SmirkHipError("libsmirk_hip.so ABI version mismatch; rebuild")
         _LIB = L
     return _LIB

@@ -15,8 +15,8 @@ The trainer itself — dataset, logging, optimiser, the `.cpu()` copies of its v
     FirstPathLoss (smirk_amd.losses)                            -> loss, terms, loss_img smirk_trainer.py:56-72, 97-101, 134-154
     perceptual / emotion / MICA terms (:104-131)                -> `extra`: added by FirstPathLoss with their weights.  The perceptual term is
                                                                    smirk_amd.VGGPerceptualLoss, the MICA term (pre-training stage, :128-131) is
-                                                                   smirk_amd.MICA.calculate_mica_shape_loss; the emotion term (weight 0.0 in both
-                                                                   shipped configs) is computed by the caller's network
+                                                                   smirk_amd.MICA.calculate_mica_shape_loss; the emotion term (:108-119, weight 0.0
+                                                                   in both shipped configs) is `emotion_term` below over smirk_amd.ExpressionLoss
 
 `forward_first_path` is everything up to the loss head, `first_path` adds the head.  Nothing here waits for the host: the terms stay on the device until
 the caller asks for `LossTerms.as_dict()`.
@@ -71,3 +71,22 @@ def first_path(encoder, flame, renderer, generator, loss, batch, face_probabilit
     if terms.loss_img is not None:
         out['loss_img'] = terms.loss_img
     return total, terms, out
+
+
+def emotion_term(generator, emotion_loss, rendered_img, masked_img, img):
+    """smirk_trainer.py:108-119: the emotion term of the first path, for the callers whose config has loss_weights['emotion_loss'] > 0.  The generator runs
+    a second time, frozen and in .eval() (its running statistics), inside the graph: the gradient passes through it into `rendered_img` and from there into the
+    encoder, and none of the generator's parameters receives one.  Afterwards the parameters require grad again, as in the reference, and the generator is back
+    in the mode it was in (the reference calls .train(): its generator is always in train mode at this point).  `emotion_loss`: a smirk_amd.ExpressionLoss.
+    Returns emotion_loss(reconstructed_img_p, img, metric='l2', use_mean=False).mean(); pass it to `first_path` as extra={'emotion_loss': ...}."""
+    was_training = generator.training
+    for param in generator.parameters():
+        param.requires_grad_(False)
+    generator.eval()
+    try:
+        reconstructed_img_p = generator(torch.cat([rendered_img, masked_img], dim=1))
+    finally:
+        for param in generator.parameters():
+            param.requires_grad_(True)
+        generator.train(was_training)
+    return emotion_loss(reconstructed_img_p, img, metric='l2', use_mean=False).mean()
