@@ -245,6 +245,33 @@ EMOTION_SIGS = {
 }
 EMOTION_EXPORTS = tuple(EMOTION_SIGS)
 
+# The extension table of include/smirk_optim.h (the trainer's optimiser stage: clip_grad_norm_ and Adam as multi-tensor kernels): the same shared object, a
+# version of its own.
+OPTIM_ABI_VERSION = 1
+OPTIM_CHUNK = 4096                                                     # include/smirk_optim.h SMIRK_OPTIM_CHUNK
+OPTIM_KIND_NORM, OPTIM_KIND_SCALE, OPTIM_KIND_ADAM = 1, 2, 4           # SMIRK_OPTIM_KIND_*
+
+
+class SmirkOptimTensor(C.Structure):
+    _fields_ = [("param", _p), ("exp_avg", _p), ("exp_avg_sq", _p), ("numel", C.c_longlong), ("first_chunk", C.c_int32), ("_pad", C.c_int32)]
+
+
+class SmirkOptimStep(C.Structure):
+    _fields_ = [("grad", _p), ("step_size", C.c_float), ("bias_correction2_sqrt", C.c_float)]
+
+
+_ll = C.c_longlong
+OPTIM_SIGS = {
+    "smirk_optim_abi_version": (_i, []),
+    "smirk_optim_plan": (_i, [C.POINTER(SmirkOptimTensor), C.POINTER(SmirkOptimStep), _i, _i, C.POINTER(_ll)]),
+    "smirk_optim_chunk_map": (_i, [C.POINTER(SmirkOptimTensor), _i, _p, _ll]),
+    "smirk_optim_grad_norm_workspace_bytes": (_sz, [_ll]),
+    "smirk_optim_grad_norm": (_i, [_p, _p, _p, _i, _ll, C.c_float, _p, _sz, _p, _p]),
+    "smirk_optim_scale_grads": (_i, [_p, _p, _p, _i, _ll, _p, _p]),
+    "smirk_optim_adam_step": (_i, [_p, _p, _p, _i, _ll, C.c_double, C.c_double, C.c_double, _p, _p]),
+}
+OPTIM_EXPORTS = tuple(OPTIM_SIGS)
+
 _LIB = None
 
 
@@ -260,11 +287,12 @@ def lib():
             raise SmirkHipError(f"{LIB_PATH} not found: build it with `python -m smirk_amd.build` "
                                 "(smirk_amd has no CPU / eager fallback)")
         L = C.CDLL(LIB_PATH)
-        for table in (_SIGS, MICA_SIGS, EMOTION_SIGS):
+        for table in (_SIGS, MICA_SIGS, EMOTION_SIGS, OPTIM_SIGS):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)       # AttributeError => header / library mismatch
                 fn.restype, fn.argtypes = res, args
-        if L.smirk_abi_version() != ABI_VERSION or L.smirk_mica_abi_version() != MICA_ABI_VERSION or L.smirk_emotion_abi_version() != EMOTION_ABI_VERSION:
+        if L.smirk_abi_version() != ABI_VERSION or L.smirk_mica_abi_version() != MICA_ABI_VERSION or L.smirk_emotion_abi_version() != EMOTION_ABI_VERSION or \
+                L.smirk_optim_abi_version() != OPTIM_ABI_VERSION:
             raise SmirkHipError("libsmirk_hip.so ABI version mismatch; rebuild")
         _LIB = L
     return _LIB

@@ -25,7 +25,8 @@ ARCH = "gfx950"
 # produces the same packed forms (round 2 shipped two v_pk_add_f32 in maxfilter1d_kernel that way); tests/test_isa_cpu.py disassembles
 # the built library and fails on any v_pk_{add,mul,fma}_f32.
 COMMON = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-Wall", "-Wno-unused-function", "-fno-slp-vectorize", "-fno-vectorize"]
-PER_FILE = {"render.hip": ["-ffp-contract=off"], "video.hip": ["-ffp-contract=off"]}
+# optim.hip: torch's Adam rounds every product and sum on its own (include/smirk_optim.h)
+PER_FILE = {"render.hip": ["-ffp-contract=off"], "video.hip": ["-ffp-contract=off"], "optim.hip": ["-ffp-contract=off"]}
 
 
 def sources():
@@ -43,7 +44,7 @@ def build(force=False, verbose=True):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(LIBDIR, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    headers += [os.path.join(os.path.dirname(HERE), "include", f) for f in ("smirk_hip.h", "smirk_mica.h", "smirk_emotion.h")]
+    headers += [os.path.join(os.path.dirname(HERE), "include", f) for f in ("smirk_hip.h", "smirk_mica.h", "smirk_emotion.h", "smirk_optim.h")]
     objs, jobs = [], []
     for s in sources():
         src = os.path.join(CSRC, s)

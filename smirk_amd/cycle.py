@@ -1,7 +1,8 @@
 """The compute of the reference trainer's cycle path (BASELINE config 5; smirk_trainer.py:184-332 `step2`, :349-382 `step`) over the smirk_amd modules.
 
 The trainer itself — dataset, logging, optimiser schedule — is the reference's and stays the reference's (caller of the hot path, out of
-scope).  The parameter augmentation that opens `step2` (smirk_trainer.py:192-248) is smirk_amd.augment (two HIP launches, no host synchronisation);
+scope); the arithmetic of its optimiser stage — the gradient clip and the two Adam steps — has a HIP form in smirk_amd.optim (`optimiser_stage` below).
+The parameter augmentation that opens `step2` (smirk_trainer.py:192-248) is smirk_amd.augment (two HIP launches, no host synchronisation);
 `second_path` chains it with `render_second_path`.  What the trainer asks of the modules per step is restated here so that tests and bench.py can drive
 exactly that sequence:
 
@@ -82,6 +83,25 @@ def cycle_forward(generator, encoder, rendered, masked, flame_feats, freeze_gene
         recon = recon.detach()
     feats = encoder(recon)
     return cycle_loss(feats, flame_feats, use_eyelids, freeze_generator), recon, feats
+
+
+def optimiser_stage(generator_params, encoder_optimizer, generator_optimizer, max_norm=0.1, step_encoder=True, step_generator=True):
+    """smirk_trainer.py:378-382 after `backward()`: clip the generator's gradients to `max_norm` (only when the generator learns in this step, as there), then
+    the optimiser steps (base_trainer.py:123-127).  With a `smirk_amd.Adam` generator optimiser the clip is deferred: the norm and the coefficient are computed
+    (two launches) and the step applies the coefficient in registers, so the gradients are read once and stay UNSCALED in memory; the updated parameters are
+    bit-identical to clipping in place first.  Any other optimiser gets the in-place clip and a plain step.  Returns the total norm (None when not clipped)."""
+    from .optim import Adam, clip_grad_norm_
+    norm = None
+    if step_encoder:
+        encoder_optimizer.step()
+    if step_generator:
+        if isinstance(generator_optimizer, Adam):
+            norm, coef = clip_grad_norm_(generator_params, max_norm, defer=True)
+            generator_optimizer.step(grad_scale=coef)
+        else:
+            norm = clip_grad_norm_(generator_params, max_norm)
+            generator_optimizer.step()
+    return norm
 
 
 CYCLE_GRAD_KEYS = ("expression_params", "jaw_params", "eyelid_params", "shape_params")        # what cycle_loss differentiates (smirk_trainer.py:304-313)
