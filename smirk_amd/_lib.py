@@ -272,6 +272,16 @@ OPTIM_SIGS = {
 }
 OPTIM_EXPORTS = tuple(OPTIM_SIGS)
 
+# The extension table of include/smirk_handoff.h (masking -> generator hand-off of the inference path: one launch for masked_img and the generator's packed
+# input, and the generator entry that starts from it): the same shared object, a version of its own.
+HANDOFF_ABI_VERSION = 1
+HANDOFF_SIGS = {
+    "smirk_handoff_abi_version": (_i, []),
+    "smirk_masking_handoff": (_i, [_p, _p, _p, _ll, _p, _i, _i, _i, C.c_float, C.c_uint64, C.c_uint64, C.c_uint64, _p, _p, _p]),
+    "smirk_generator_forward_packed": (_i, [C.POINTER(SmirkGeneratorWeights), _p, _p, _i, _i, _i, C.POINTER(_p), _p, _sz, _p]),
+}
+HANDOFF_EXPORTS = tuple(HANDOFF_SIGS)
+
 _LIB = None
 
 
@@ -287,12 +297,12 @@ def lib():
             raise SmirkHipError(f"{LIB_PATH} not found: build it with `python -m smirk_amd.build` "
                                 "(smirk_amd has no CPU / eager fallback)")
         L = C.CDLL(LIB_PATH)
-        for table in (_SIGS, MICA_SIGS, EMOTION_SIGS, OPTIM_SIGS):
+        for table in (_SIGS, MICA_SIGS, EMOTION_SIGS, OPTIM_SIGS, HANDOFF_SIGS):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)       # AttributeError => header / library mismatch
                 fn.restype, fn.argtypes = res, args
         if L.smirk_abi_version() != ABI_VERSION or L.smirk_mica_abi_version() != MICA_ABI_VERSION or L.smirk_emotion_abi_version() != EMOTION_ABI_VERSION or \
-                L.smirk_optim_abi_version() != OPTIM_ABI_VERSION:
+                L.smirk_optim_abi_version() != OPTIM_ABI_VERSION or L.smirk_handoff_abi_version() != HANDOFF_ABI_VERSION:
             raise SmirkHipError("libsmirk_hip.so ABI version mismatch; rebuild")
         _LIB = L
     return _LIB

@@ -10,7 +10,8 @@
 //   bernoulli_field / masking_compose / transfer_pixels                                        (masking.py:71-102,116-129)
 // Random draws are reproducible from (seed, call offset) but are NOT torch's CPU/CUDA streams — the reference itself draws
 // different numbers on CPU and GPU; deterministic entry points (coords= / explicit fields) are what the parity tests pin.
-#include "common.h"
+#include "conv_common.h"
+#include "../../include/smirk_handoff.h"
 
 // ---- Philox4x32-10 (Salmon et al. 2011), counter = (idx, stream, 0, 0), key = seed ------------------------------------------------
 __device__ __forceinline__ void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
@@ -217,6 +218,25 @@ __global__ __launch_bounds__(256) void bernoulli_field_kernel(float* __restrict_
         if (i4 + k < n) out[i4 + k] = u01(r[k]) < p ? 1.0f : 0.0f;
 }
 
+// One element of masking(): masked = x * m; e = extra value (* noise) (* keep); out = e > 0 ? e : masked (masking.py:91-101).  The one place the expression is
+// spelled: masking_compose_kernel and masking_handoff_kernel both call it, so the compiler contracts it the same way in both.  The generated noise is
+// N(1, 0.05) by Box-Muller from Philox block `ctr` of stream 2.  Where e == 0 the draw is skipped: e * noise * keep is +-0 whatever the (finite) noise is, `e > 0`
+// is false and the output is `masked` either way.  The comparison is false for a NaN, which takes the full path as before.
+__device__ __forceinline__ float masking_compose1(float x, float m, float e, const float* noise_mult, int gen_noise, uint64_t seed, uint64_t ctr,
+                                                  bool has_keep, float keep) {
+    const float masked = x * m;
+    if (noise_mult) e = e * *noise_mult;
+    else if (gen_noise && !(e == 0.0f)) {
+        uint32_t r[4];
+        philox4x32((uint32_t)ctr, (uint32_t)(ctr >> 32), 2u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+        const float u1 = fmaxf(u01(r[0]), 5.96e-8f), u2 = u01(r[1]);
+        const float z = sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);      // Box-Muller
+        e = e * (z * 0.05f + 1.0f);                                                          // masking.py:91-92
+    }
+    if (has_keep) e = e * keep;
+    return (e > 0.0f) ? e : masked;                                                          // masking.py:101
+}
+
 // masked = img * mask * (1 - rendered_mask); extra = extra_points * (noise ? N(1, 0.05) : 1) * keep; out = extra > 0 ? extra : masked
 // img / extra / out [B][C][H][W]; mask, rendered_mask, keep [B][1][H][W] (rendered_mask / keep nullable)
 __global__ __launch_bounds__(256) void masking_compose_kernel(const float* __restrict__ img, const float* __restrict__ mask,
@@ -231,19 +251,173 @@ __global__ __launch_bounds__(256) void masking_compose_kernel(const float* __res
     const size_t b = i / ((size_t)C * HW), p = i % HW;
     float m = mask[b * HW + p];
     if (rendered_mask) m = m * (1.0f - rendered_mask[b * HW + p]);
-    const float masked = img[i] * m;
-    float e = extra ? extra[i] : img[i] * pmask[b * HW + p];                                 // demo.py:163 extra_points = image * pmask
-    if (noise_mult) e = e * noise_mult[i];
-    else if (gen_noise) {
-        uint32_t r[4];
-        const uint64_t ctr = offset + i;
-        philox4x32((uint32_t)ctr, (uint32_t)(ctr >> 32), 2u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-        const float u1 = fmaxf(u01(r[0]), 5.96e-8f), u2 = u01(r[1]);
-        const float z = sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);      // Box-Muller
-        e = e * (z * 0.05f + 1.0f);                                                          // masking.py:91-92
+    const float e = extra ? extra[i] : img[i] * pmask[b * HW + p];                           // demo.py:163 extra_points = image * pmask
+    out[i] = masking_compose1(img[i], m, e, noise_mult ? noise_mult + i : nullptr, gen_noise, seed, offset + i, keep != nullptr,
+                              keep ? keep[b * HW + p] : 0.0f);
+}
+
+// ---- masking -> generator hand-off in ONE launch (include/smirk_handoff.h) ------------------------------------------------------------------
+// What demo_masked_image -> SmirkGenerator.forward_pair ran as six launches (rendered_mask, maxpool_sq<10>, bernoulli_field, maxpool_sq<5>, masking_compose,
+// pack_split): a workgroup owns HO_ROWS rows of one image over the full width and reads only img, rendered_img, the hull mask and pmask.
+//   1  stage 1 - hull for rows [y0 - 10, y0 + HO_ROWS + 10) (A1) and draw the Bernoulli patch centres for rows [y0 - 5, y0 + HO_ROWS + 5) (A2): pixel i of the
+//      [B][H][W] field is lane i % 4 of Philox block offset + i / 4 of stream 1, as bernoulli_field_kernel draws it, so a halo pixel is recomputed and never read;
+//      -inf outside the image and in the margins, as the max pool pads
+//   2  the x passes (21 and 11 taps) IN PLACE: a wave owns a whole staged row and walks it left to right, every lane reads its 4 + 2R window with ds_read_b128
+//      (conflict-free, see maxpool_sq_lds_kernel) and writes its 4 maxima at the window's first 4 cells.  Reads precede the write in the wave's program order (LDS
+//      operations of a wave retire in order) and a later 256-column step reads only cells at or right of its own outputs, so no second image of the rows is needed
+//   3  per thread 4 rows of one column: the y passes from LDS (lanes are neighbouring x: conflict-free), the rendered mask from the three rendered_img values that
+//      are loaded for the pack anyway, the composition (masking_compose1), masked_img and the split-fp16 NHWC group of pack_split_kernel
+// LDS: (HO_ROWS + 20) * mp_row_stride(W, 10) + (HO_ROWS + 10) * mp_row_stride(W, 5) floats = 61,248 bytes at W = 224: two workgroups per CU.
+#define HO_ROWS 16
+#define HO_THREADS 512
+#define HO_R1 10                                    // masking.py:78 through demo.py:161: the hull mask's erosion radius
+#define HO_R2 5                                     // masking.py:96: 11 x 11 patches
+static inline size_t ho_lds_bytes(int W) {
+    return ((size_t)(HO_ROWS + 2 * HO_R1) * mp_row_stride(W, HO_R1) + (size_t)(HO_ROWS + 2 * HO_R2) * mp_row_stride(W, HO_R2)) * sizeof(float);
+}
+
+// A[rr][x] <- max(A[rr][x .. x + 2R]) for x < W, rr < NR; A[rr][c] holds column c - R on entry
+template <int R>
+__device__ __forceinline__ void ho_xpass_inplace(float* A, int NR, int SW, int W) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int W4 = (W + 3) / 4;
+    for (int rr = wave; rr < NR; rr += HO_THREADS / 64) {
+        for (int x4 = lane; x4 < W4; x4 += 64) {
+            float* a = A + rr * SW + x4 * 4;                     // 16-byte aligned: SW is a multiple of 4
+            const f32x4* a4 = (const f32x4*)a;
+            constexpr int NV = (4 + 2 * R + 3) / 4;
+            float v[4 * NV];
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+                const f32x4 t = a4[j];
+                v[4 * j] = t[0]; v[4 * j + 1] = t[1]; v[4 * j + 2] = t[2]; v[4 * j + 3] = t[3];
+            }
+            float c = v[3];
+#pragma unroll
+            for (int k = 4; k <= 2 * R; ++k) c = fmaxf(c, v[k]);
+            const f32x4 o = {fmaxf(fmaxf(c, v[2]), fmaxf(v[1], v[0])), fmaxf(fmaxf(c, v[2]), fmaxf(v[1], v[2 * R + 1])),
+                             fmaxf(fmaxf(c, v[2]), fmaxf(v[2 * R + 2], v[2 * R + 1])), fmaxf(fmaxf(c, v[2 * R + 3]), fmaxf(v[2 * R + 2], v[2 * R + 1]))};
+            *(f32x4*)a = o;                                      // cells x4 * 4 + 3 >= W of a ragged row lie in the margin, which nobody reads again
+        }
     }
-    if (keep) e = e * keep[b * HW + p];
-    out[i] = (e > 0.0f) ? e : masked;                                                        // masking.py:101
+}
+
+// 4 consecutive outputs of a (2R+1)-tap column maximum: o[k] = max(h[(k .. k + 2R) * SW])
+template <int R>
+__device__ __forceinline__ void ho_ypass4(const float* h, int SW, float* o) {
+    float v[4 + 2 * R];
+#pragma unroll
+    for (int k = 0; k < 4 + 2 * R; ++k) v[k] = h[k * SW];
+    float c = v[3];
+#pragma unroll
+    for (int k = 4; k <= 2 * R; ++k) c = fmaxf(c, v[k]);
+    o[0] = fmaxf(fmaxf(c, v[2]), fmaxf(v[1], v[0]));
+    o[1] = fmaxf(fmaxf(c, v[2]), fmaxf(v[1], v[2 * R + 1]));
+    o[2] = fmaxf(fmaxf(c, v[2]), fmaxf(v[2 * R + 2], v[2 * R + 1]));
+    o[3] = fmaxf(fmaxf(c, v[2 * R + 3]), fmaxf(v[2 * R + 2], v[2 * R + 1]));
+}
+
+// img / rendered / masked [B][3][H][W]; hull [B or 1][H][W] with batch stride hull_bs (0 or H * W); pmask [B][H][W]; packed [B][H][W][8] split-fp16 (32 bytes a pixel)
+__global__ __launch_bounds__(HO_THREADS) void masking_handoff_kernel(const float* __restrict__ img, const float* __restrict__ rendered,
+                                                                      const float* __restrict__ hull, size_t hull_bs, const float* __restrict__ pmask,
+                                                                      int H, int W, float p_field, uint64_t seed, uint64_t field_offset,
+                                                                      uint64_t noise_offset, float* __restrict__ masked, float* __restrict__ packed) {
+    extern __shared__ __attribute__((aligned(16))) float ho_lds[];
+    const int SW1 = mp_row_stride(W, HO_R1), SW2 = mp_row_stride(W, HO_R2);
+    constexpr int NR1 = HO_ROWS + 2 * HO_R1, NR2 = HO_ROWS + 2 * HO_R2;
+    float* A1 = ho_lds;                                 // [NR1][SW1]  1 - hull, then its x maxima
+    float* A2 = ho_lds + NR1 * SW1;                     // [NR2][SW2]  patch centres, then their x maxima
+    const int tiles = (H + HO_ROWS - 1) / HO_ROWS;
+    const int b = blockIdx.x / tiles, y0 = (blockIdx.x % tiles) * HO_ROWS;
+    const size_t HW = (size_t)H * W;
+    const int tid = threadIdx.x;
+    // ---- 1a: the hull rows (eight requests in flight per lane and trip, clamped addresses + select, as maxpool_sq_lds_kernel stages them) ----
+    const float* hsrc = hull + (size_t)b * hull_bs;
+    for (int base = 0; base < NR1 * SW1; base += HO_THREADS * 8) {
+        float sv[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int i = base + HO_THREADS * u + tid, rr = i / SW1, cx = i - rr * SW1 - HO_R1, y = y0 - HO_R1 + rr;
+            const bool in = i < NR1 * SW1 && y >= 0 && y < H && cx >= 0 && cx < W;
+            const float t = hsrc[(size_t)min(max(y, 0), H - 1) * W + min(max(cx, 0), W - 1)];
+            sv[u] = in ? 1.0f - t : -INFINITY;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int i = base + HO_THREADS * u + tid;
+            if (i < NR1 * SW1) A1[i] = sv[u];
+        }
+    }
+    // ---- 1b: the patch-centre rows.  Cells outside the image first, then one Philox block per 4 consecutive pixels of the flat field (disjoint cells: no barrier) ----
+    for (int i = tid; i < NR2 * SW2; i += HO_THREADS) {
+        const int rr = i / SW2, cx = i - rr * SW2 - HO_R2, y = y0 - HO_R2 + rr;
+        if (!(y >= 0 && y < H && cx >= 0 && cx < W)) A2[i] = -INFINITY;
+    }
+    {
+        const int ylo = max(y0 - HO_R2, 0), yhi = min(y0 + HO_ROWS + HO_R2, H);
+        const size_t img0 = (size_t)b * HW, s = img0 + (size_t)ylo * W, e = img0 + (size_t)yhi * W;
+        for (size_t g = s / 4 + tid; g * 4 < e; g += HO_THREADS) {
+            uint32_t r[4];
+            const uint64_t ctr = field_offset + g;
+            philox4x32((uint32_t)ctr, (uint32_t)(ctr >> 32), 1u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const size_t i = g * 4 + k;
+                if (i >= s && i < e) {
+                    const int rel = (int)(i - img0), y = rel / W, x = rel - y * W;
+                    A2[(y - (y0 - HO_R2)) * SW2 + x + HO_R2] = u01(r[k]) < p_field ? 1.0f : 0.0f;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // ---- 2: x passes in place ----
+    ho_xpass_inplace<HO_R1>(A1, NR1, SW1, W);
+    ho_xpass_inplace<HO_R2>(A2, NR2, SW2, W);
+    __syncthreads();
+    // ---- 3: y passes, composition, both stores ----
+    const float* ib = img + (size_t)b * 3 * HW;
+    const float* rb = rendered + (size_t)b * 3 * HW;
+    const float* pb = pmask + (size_t)b * HW;
+    float* mb = masked + (size_t)b * 3 * HW;
+    float* kb = packed + (size_t)b * HW * 8;
+    for (int i = tid; i < (HO_ROWS / 4) * W; i += HO_THREADS) {
+        const int q = i / W, x = i - q * W;
+        float er[4], dl[4];
+        ho_ypass4<HO_R1>(A1 + (q * 4) * SW1 + x, SW1, er);        // staged row q*4 + k = image row y0 + q*4 - R + k
+        ho_ypass4<HO_R2>(A2 + (q * 4) * SW2 + x, SW2, dl);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int y = y0 + q * 4 + k;
+            if (y >= H) continue;
+            const size_t pix = (size_t)y * W + x;
+            float mask_d = 1.0f - er[k], keep = 1.0f - dl[k];     // what the two max pools stored: 1 - maxpool(1 - mask), 1 - maxpool(centres)
+            asm("" : "+v"(mask_d));                               // rounded fp32 values, as when they came back from memory
+            asm("" : "+v"(keep));
+            const float pm = pb[pix];
+            float v[8];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c] = rb[c * HW + pix];
+            const bool all0 = v[0] == 0.0f && v[1] == 0.0f && v[2] == 0.0f;
+            float rm = all0 ? 0.0f : 1.0f;                        // rendered_mask_kernel
+            asm("" : "+v"(rm));
+            const float m = mask_d * (1.0f - rm);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float xin = ib[c * HW + pix];
+                const float o = masking_compose1(xin, m, xin * pm, nullptr, 1, seed, noise_offset + ((size_t)b * 3 + c) * HW + pix, true, keep);
+                mb[c * HW + pix] = o;
+                v[3 + c] = o;
+            }
+            v[6] = 0.f; v[7] = 0.f;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) smirk_range_audit1(v[c]);  // the network INPUT, as pack_split_kernel audits it
+            half8 hi, lo;
+            split8(v, hi, lo);
+            *(half8*)(kb + pix * 8) = hi;
+            *(half8*)(kb + pix * 8 + 4) = lo;
+        }
+    }
 }
 
 // retained[b,:,p2y,p2x] = img[b,:,p1y,p1x] for l < rbound[b]; duplicates in points2: the highest l wins (CPU index_put order)
@@ -405,5 +579,25 @@ __global__ __launch_bounds__(256) void point_budget_kernel(long long* __restrict
 extern "C" int smirk_random_point_budget(int64_t* rbound, int B, int n_points, float mul, uint64_t seed, uint64_t offset, void* stream) {
     if (!rbound || B <= 0 || n_points <= 0 || !(mul >= 1.0f)) return SMIRK_ERR_BAD_ARG;
     SMIRK_LAUNCH(point_budget_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, (long long*)rbound, B, n_points, mul, seed, offset);
+    return smirk_launch_status();
+}
+
+// ---- include/smirk_handoff.h -------------------------------------------------------------------------------------------------------------------------------
+extern "C" int smirk_handoff_abi_version(void) { return SMIRK_HANDOFF_ABI_VERSION; }
+
+extern "C" int smirk_masking_handoff(const float* img, const float* rendered_img, const float* hull_mask, long long hull_batch_stride, const float* pmask,
+                                     int B, int H, int W, float random_mask, uint64_t seed, uint64_t field_offset, uint64_t noise_offset, float* masked_img,
+                                     void* packed, void* stream) {
+    if (!img || !rendered_img || !hull_mask || !pmask || !masked_img || !packed || B <= 0 || H <= 0 || W <= 0) return SMIRK_ERR_BAD_ARG;
+    if (hull_batch_stride != 0 && hull_batch_stride != (long long)H * W) return SMIRK_ERR_BAD_ARG;
+    if (!(random_mask > 0.0f)) return SMIRK_ERR_BAD_ARG;                                            // masking() draws no field then: that path keeps its launches
+    const size_t lds = ho_lds_bytes(W);
+    const long long tiles = (H + HO_ROWS - 1) / HO_ROWS;
+    // two workgroups per CU need at most 80 KB each; the flat field index of a pixel is taken relative to its image in 32 bits
+    if (lds > 80 * 1024 || (long long)B * tiles >= 0x7fffffffll || (long long)H * W >= 0x7fffffffll) return SMIRK_ERR_UNSUPPORTED;
+    if (smirk_raise_dynamic_lds((const void*)masking_handoff_kernel, 80 * 1024) != SMIRK_OK) return SMIRK_ERR_UNSUPPORTED;
+    smirk_prof_next(nullptr, 0.0, (double)B * H * W * (4.0 * (3 + 3 + 1 + 1 + 3) + 32.0));
+    SMIRK_LAUNCH(masking_handoff_kernel, dim3((unsigned)(B * tiles)), dim3(HO_THREADS), lds, (hipStream_t)stream, img, rendered_img, hull_mask,
+                 (size_t)hull_batch_stride, pmask, H, W, random_mask, seed, field_offset, noise_offset, masked_img, (float*)packed);
     return smirk_launch_status();
 }

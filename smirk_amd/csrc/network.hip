@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include "conv_common.h"
+#include "../../include/smirk_handoff.h"
 
 namespace {
 
@@ -114,17 +115,19 @@ extern "C" size_t smirk_generator_workspace_bytes(const SmirkGeneratorWeights* w
     return plan_generator(w, B, H, W, nullptr).total;
 }
 
-extern "C" int smirk_generator_forward(const SmirkGeneratorWeights* w, const float* a, int Ca, const float* b, int Cb, float* y, int B, int H,
-                                       int W, void* const* taps, void* ws, size_t ws_bytes, void* stream) {
-    if (!gen_args_ok(w, B, H, W) || !a || !y || !ws || Ca <= 0 || Cb < 0 || Ca + Cb != w->in_channels || (Cb > 0 && !b)) return SMIRK_ERR_BAD_ARG;
-    if (!w->final_w || !w->final_b) return SMIRK_ERR_BAD_ARG;
+// The one body of the two whole-network entries: smirk_generator_forward packs cat(a, b) into the workspace first, smirk_generator_forward_packed
+// (include/smirk_handoff.h) hands in `packed`, the same tensor written by masking_handoff_kernel, and the pack step is left out.
+static int generator_forward_body(const SmirkGeneratorWeights* w, const float* a, int Ca, const float* b, int Cb, const void* packed, float* y, int B, int H,
+                                  int W, void* const* taps, void* ws, size_t ws_bytes, void* stream) {
     const GenPlan p = plan_generator(w, B, H, W, ws);
     if (ws_bytes < p.total) return SMIRK_ERR_WORKSPACE;
     const bool split = w->precision == SMIRK_PRECISION_F16X3;
     const int f = w->features;
 
     // ---- cat + NCHW -> NHWC (+ split) of the network input (smirk_trainer.py:94, demo.py:167) ----------------------------------------
-    if (split) {
+    if (packed) {
+        // already in the network's input format
+    } else if (split) {
         TRY(smirk_pack_generator_input_split16(a, Ca, b, Cb, p.x, B, H, W, stream));
     } else if (Cb == 0) {
         TRY(smirk_nchw_to_nhwc_pad(a, (float*)p.x, B, Ca, H, W, w->cin_pad, stream));
@@ -205,7 +208,7 @@ extern "C" int smirk_generator_forward(const SmirkGeneratorWeights* w, const flo
         }
     }
     // ---- encoder levels above the section, whole batch (smirk_generator.py:52-57) --------------------------------------------------------------------------
-    const void* cur = p.x;
+    const void* cur = packed ? packed : p.x;
     int cin = w->cin_pad;
     for (int l = 0; l < L0; ++l) {
         const int h = H >> l, wd = W >> l, c = f << l;
@@ -355,6 +358,20 @@ extern "C" int smirk_generator_forward(const SmirkGeneratorWeights* w, const flo
     }
     return split ? smirk_conv1x1_sigmoid_nchw_split16(dcur, w->final_w, w->final_b, y, B, H, W, f, w->out_channels, stream)
                  : smirk_conv1x1_sigmoid_nchw((const float*)dcur, w->final_w, w->final_b, y, B, H, W, f, w->out_channels, stream);
+}
+
+extern "C" int smirk_generator_forward(const SmirkGeneratorWeights* w, const float* a, int Ca, const float* b, int Cb, float* y, int B, int H,
+                                       int W, void* const* taps, void* ws, size_t ws_bytes, void* stream) {
+    if (!gen_args_ok(w, B, H, W) || !a || !y || !ws || Ca <= 0 || Cb < 0 || Ca + Cb != w->in_channels || (Cb > 0 && !b)) return SMIRK_ERR_BAD_ARG;
+    if (!w->final_w || !w->final_b) return SMIRK_ERR_BAD_ARG;
+    return generator_forward_body(w, a, Ca, b, Cb, nullptr, y, B, H, W, taps, ws, ws_bytes, stream);
+}
+
+extern "C" int smirk_generator_forward_packed(const SmirkGeneratorWeights* w, const void* packed, float* y, int B, int H, int W, void* const* taps, void* ws,
+                                              size_t ws_bytes, void* stream) {
+    if (!gen_args_ok(w, B, H, W) || w->precision != SMIRK_PRECISION_F16X3 || !packed || !y || !ws) return SMIRK_ERR_BAD_ARG;
+    if (!w->final_w || !w->final_b) return SMIRK_ERR_BAD_ARG;
+    return generator_forward_body(w, nullptr, 0, nullptr, 0, packed, y, B, H, W, taps, ws, ws_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------

@@ -25,7 +25,12 @@
 //                                   smirk_conv_wgrad_set_mode overrides it                                                                set_mode)
 //
 // Switches read by the Python package, not here: SMIRK_AMD_*_PRECISION, SMIRK_ENCODER_SERIAL, SMIRK_ENCODER_TRAIN_SERIAL, SMIRK_BN_STATS_UNFUSED,
-// SMIRK_F16X3_RANGE_CHECK, SMIRK_HIP_LIBRARY.
+// SMIRK_F16X3_RANGE_CHECK, SMIRK_HIP_LIBRARY, and
+// SMIRK_DISABLE_MASKING_HANDOFF     set (any value): masking.demo_masked_image_packed, and with it the hull_mask= path of the pipelines, keeps the six separate
+//                                   launches (rendered mask, two max pools, patch-centre field, composition, the generator's pack) instead of
+//                                   masking_handoff_kernel + smirk_generator_forward_packed; same output bits (tests/test_masking_handoff_gpu.py,
+//                                   tests/test_generator_packed_gpu.py).  The choice between the two is made where the tensors are allocated, in Python, so the
+//                                   variable is read there and is not a member of the enum below.
 #pragma once
 
 #define SMIRK_WGRAD_F16_DEFAULT 2

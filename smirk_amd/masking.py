@@ -10,6 +10,8 @@ landmark gather, pixel quantisation, separable max-pool dilations and the final 
 Philox stream keyed by torch's global seed (`torch.manual_seed`) and a call counter — reproducible, but (like the reference's own CPU
 vs CUDA runs) not the same numbers as torch's generators; pass `coords=` for deterministic geometry, exactly as the reference allows.
 """
+import os
+
 import numpy as np
 import torch
 
@@ -212,13 +214,9 @@ def points_mask(npoints, H, W, rbound=None):
     return out
 
 
-def demo_masked_image(img, hull_mask, rendered_img, transformed_vertices, flame_faces, face_probabilities,
-                      mask_ratio=0.01, mask_ratio_mul=5, mask_dilation_radius=10, rng=None):
-    """The block demo.py:138-165 runs between Renderer and SmirkGenerator, on the GPU: rendered mask, mesh-based point sampling with a
-    random per-image budget, point mask, masking().  Returns masked_img [B,3,H,W].  `rng`: an optional PhiloxStream that pins every
-    draw of the block (sampled faces + barycentrics, per-image budgets, patch centres, point noise) independently of torch's generators."""
+def _demo_points_mask(img, transformed_vertices, flame_faces, face_probabilities, mask_ratio, mask_ratio_mul, rng):
+    """demo.py:148-159: the sampled mesh points of a random per-image budget as a [B,1,H,W] mask.  Draws, in this order: points, budgets."""
     B, _, H, W = img.shape
-    rmask = rendered_mask_of(rendered_img)
     npoints, _ = mesh_based_mask_uniform_faces(transformed_vertices, flame_faces, face_probabilities, mask_ratio=mask_ratio * mask_ratio_mul,
                                                IMAGE_SIZE=H, _rng_stream=rng)
     # demo.py:154-156 draws rsing / rscale per image on the host and copies the budgets over; here they are drawn on the device (Philox keyed
@@ -226,5 +224,59 @@ def demo_masked_image(img, hull_mask, rendered_img, transformed_vertices, flame_
     rbound = torch.empty(B, dtype=torch.int64, device=img.device)
     seed, off = _rng(B, rng)
     L.check(L.lib().smirk_random_point_budget(L.ptr(rbound, torch.int64), B, int(npoints.size(1)), float(mask_ratio_mul), seed, off, L.stream_ptr()))
-    pmask = points_mask(npoints, H, W, rbound)
+    return points_mask(npoints, H, W, rbound)
+
+
+def demo_masked_image_packed(img, hull_mask, rendered_img, transformed_vertices, flame_faces, face_probabilities,
+                             mask_ratio=0.01, mask_ratio_mul=5, mask_dilation_radius=10, rng=None, random_mask=0.01):
+    """demo_masked_image for a caller that hands the result to SmirkGenerator.forward_packed: -> (masked_img [B,3,H,W], packed [B,H,W,8]), where `packed` is
+    the generator's split-fp16 network input of cat(rendered_img, masked_img).  One launch (smirk_masking_handoff, include/smirk_handoff.h) stands for the
+    rendered mask, both max pools, the patch-centre field, the composition and the generator's pack; both tensors equal bit for bit what demo_masked_image and
+    the generator's own pack produce under the same draws (the Philox offsets are allocated in the same order: points, budgets, field, noise).  `packed` is
+    None where that launch does not serve the call (a radius other than 10, other than 3 channels, random_mask == 0, rows too wide for its LDS band) or
+    $SMIRK_DISABLE_MASKING_HANDOFF is set (the A/B switch of tests/test_masking_handoff_gpu.py, csrc/switches.h): masked_img then comes from the separate
+    launches, under the same draws, and the caller packs as before."""
+    img, rendered = L.as_f32c(img), L.as_f32c(rendered_img)
+    B, C, H, W = img.shape
+    hull = L.as_f32c(hull_mask)
+    if hull.dim() == 4 and hull.shape[1] == 1:
+        hull = hull[:, 0]
+    fused = C == 3 and rendered.shape == img.shape and mask_dilation_radius == 10 and random_mask > 0 and hull.dim() == 3 \
+        and hull.shape[0] in (1, B) and tuple(hull.shape[1:]) == (H, W) and not os.environ.get("SMIRK_DISABLE_MASKING_HANDOFF")
+    rmask = None if fused else rendered_mask_of(rendered)
+    pmask = _demo_points_mask(img, transformed_vertices, flame_faces, face_probabilities, mask_ratio, mask_ratio_mul, rng)
+    if not fused:
+        return masking(img, hull_mask, None, mask_dilation_radius, rendered_mask=rmask, random_mask=random_mask, _pmask=pmask, _rng_stream=rng), None
+    seed, field_off = _rng((B * H * W + 3) // 4, rng)
+    _, noise_off = _rng(img.numel(), rng)
+    masked = torch.empty_like(img)
+    packed = torch.empty(B, H, W, 8, device=img.device)
+    hull = hull.contiguous()
+    code = L.lib().smirk_masking_handoff(L.ptr(img), L.ptr(rendered), L.ptr(hull), H * W if hull.shape[0] == B and B > 1 else 0, L.ptr(pmask), B, H, W,
+                                         float(random_mask), seed, field_off, noise_off, L.ptr(masked), L.ptr(packed), L.stream_ptr())
+    if code == L.SMIRK_ERR_UNSUPPORTED:
+        # the same draws through the separate launches: the two offsets above are the ones masking() would have allocated
+        return masking(img, hull_mask, None, mask_dilation_radius, rendered_mask=rendered_mask_of(rendered), random_mask=random_mask, _pmask=pmask,
+                       _rng_stream=_Replay(seed, (field_off, noise_off))), None
+    L.check(code)
+    return masked, packed
+
+
+class _Replay:
+    """hands masking() the (seed, offset) pairs that were already drawn for it"""
+
+    def __init__(self, seed, offsets):
+        self.seed, self.offsets = seed, list(offsets)
+
+    def __call__(self, n_draws):
+        return self.seed, self.offsets.pop(0)
+
+
+def demo_masked_image(img, hull_mask, rendered_img, transformed_vertices, flame_faces, face_probabilities,
+                      mask_ratio=0.01, mask_ratio_mul=5, mask_dilation_radius=10, rng=None):
+    """The block demo.py:138-165 runs between Renderer and SmirkGenerator, on the GPU: rendered mask, mesh-based point sampling with a
+    random per-image budget, point mask, masking().  Returns masked_img [B,3,H,W].  `rng`: an optional PhiloxStream that pins every
+    draw of the block (sampled faces + barycentrics, per-image budgets, patch centres, point noise) independently of torch's generators."""
+    rmask = rendered_mask_of(rendered_img)
+    pmask = _demo_points_mask(img, transformed_vertices, flame_faces, face_probabilities, mask_ratio, mask_ratio_mul, rng)
     return masking(img, hull_mask, None, mask_dilation_radius, rendered_mask=rmask, _pmask=pmask, _rng_stream=rng)

@@ -36,6 +36,21 @@ class SmirkPipeline:
         return M.demo_masked_image(img, hull_mask, rn['rendered_img'], rn['transformed_vertices'], self.flame.faces_tensor,
                                    self.face_probabilities, rng=rng)
 
+    def generate_from_hull(self, img, hull_mask, rn, rng=None):
+        """-> (masked_img, reconstructed_img) of the hull_mask= path.  A generator that takes the packed network input (split-fp16 inference) gets it from the
+        masking stage's own launch (masking.demo_masked_image_packed: one kernel writes masked_img and the generator's input, and the generator skips its
+        pack); any other generator, and $SMIRK_DISABLE_MASKING_HANDOFF, keep masked_from_hull + forward_pair.  The outputs are the same bits either way.
+        The packed tensor is allocated here, per call, on the current stream: it belongs to this stage, not to the generator's workspace, which the next
+        batch's generator may already be using."""
+        from . import masking as M
+        g = self.generator
+        if self.face_probabilities is None or not getattr(g, "accepts_packed", lambda: False)():
+            masked = self.masked_from_hull(img, hull_mask, rn, rng)
+            return masked, g.forward_pair(rn['rendered_img'], masked)
+        masked, packed = M.demo_masked_image_packed(img, hull_mask, rn['rendered_img'], rn['transformed_vertices'], self.flame.faces_tensor,
+                                                    self.face_probabilities, rng=rng)
+        return masked, (g.forward_pair(rn['rendered_img'], masked) if packed is None else g.forward_packed(packed))
+
     @torch.no_grad()
     def __call__(self, img, masked_img=None, with_landmarks=True, hull_mask=None, mask_rng=None):
         """`mask_rng`: optional masking.PhiloxStream pinning the random draws of the hull_mask= path (default: keyed by torch's seed)."""
@@ -47,8 +62,8 @@ class SmirkPipeline:
         out.update(vertices=fl['vertices'], landmarks_fan_3d=fl['landmarks_fan_3d'], **rn)
         if self.generator is not None:
             if masked_img is None and hull_mask is not None:
-                masked_img = self.masked_from_hull(img, hull_mask, rn, mask_rng)
-                out['masked_img'] = masked_img
+                out['masked_img'], out['reconstructed_img'] = self.generate_from_hull(img, hull_mask, rn, mask_rng)
+                return out
             if masked_img is None:
                 raise ValueError("the generator needs the masked image (or hull_mask=) next to the rendering")
             out['reconstructed_img'] = self.generator.forward_pair(rn['rendered_img'], masked_img)     # torch.cat never materialised
@@ -108,11 +123,12 @@ class OverlappedPipeline:
                 g = self.pipe.generator
                 if isinstance(masked, tuple):                   # ("hull", img, hull_mask): masking utilities run with the generator stage
                     _, im, hull, rng = masked
-                    masked = self.pipe.masked_from_hull(im, hull, out, rng)
+                    masked, out['reconstructed_img'] = self.pipe.generate_from_hull(im, hull, out, rng)
                     out['masked_img'] = masked
                     for t in (out['transformed_vertices'], im, hull):
                         t.record_stream(gs)
-                out['reconstructed_img'] = g.forward_pair(out['rendered_img'], masked)
+                else:
+                    out['reconstructed_img'] = g.forward_pair(out['rendered_img'], masked)
                 for t in (out['rendered_img'], masked):
                     t.record_stream(gs)
                 done = torch.cuda.Event()

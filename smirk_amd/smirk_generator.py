@@ -229,10 +229,15 @@ class SmirkGenerator(nn.Module):
             # not a narrowing of the drop-in: the reference fails on such sizes too (4 x MaxPool2d(2) floors, 4 x ConvTranspose2d doubles, and torch.cat of
             # the skip tensor with a different size raises, smirk_generator.py:65-75)
             raise L.SmirkHipError("input size must be a multiple of 16 (4 pooling levels; the reference's torch.cat of the skip tensors fails otherwise too)")
-        lib, w = L.lib(), self._weights()
+        self._weights()                                                     # decides self._split / self._cin_pad
         if not self._split and b is not None and not (Ca == 3 and Cb == 3 and self._cin_pad == 8):
             a, b, Ca, Cb = torch.cat([a, b], 1), None, Ca + Cb, 0            # exact-fp32 mode packs two sources only for the 3 + 3 case
-        dev = a.device
+        return self._enqueue(a.device, B, H, W, taps, srcs, lambda lib, w, out, tp, ws, nws, st: lib.smirk_generator_forward(
+            w, L.ptr(a), Ca, L.ptr(b, allow_none=True), Cb, L.ptr(out), B, H, W, tp, L.ptr(ws, torch.uint8), nws, st))
+
+    def _enqueue(self, dev, B, H, W, taps, srcs, entry):
+        """output, taps, workspace and the audit around one call of a whole-network entry (smirk_generator_forward or smirk_generator_forward_packed)"""
+        lib, w = L.lib(), self._weights()
         out = torch.empty(B, self.out_channels, H, W, device=dev)
         tp = None
         audit = self._split and os.environ.get("SMIRK_F16X3_RANGE_CHECK")
@@ -246,13 +251,32 @@ class SmirkGenerator(nn.Module):
             taps.update(dict(zip(self.TAPS, bufs)))
         nws = lib.smirk_generator_workspace_bytes(w, B, H, W)
         ws = self._ws.get(nws, dev)
-        L.check(lib.smirk_generator_forward(w, L.ptr(a), Ca, L.ptr(b, allow_none=True), Cb, L.ptr(out), B, H, W, tp, L.ptr(ws, torch.uint8), nws,
-                                            L.stream_ptr()))
+        L.check(entry(lib, w, out, tp, ws, nws, L.stream_ptr()))
         if audit:
             self._range_audit(taps, float(audit) if audit not in ("1", "true") else 6.0e4)
         # the reference back-propagates through the generator (smirk_trainer.py:94-104); this forward has no backward yet, so make any
         # attempt to do so fail loudly instead of handing the caller zero / missing gradients
         return L.loud_cut("smirk_amd.SmirkGenerator.forward", out, srcs + list(self.parameters()))
+
+    def accepts_packed(self):
+        """True where forward_packed serves this module: eval mode, split-fp16 arithmetic, the 3 + 3 input channels of cat(rendered_img, masked_img)."""
+        return not self.training and self.precision == "f16x3" and self.in_channels == 6
+
+    def forward_packed(self, packed, _taps=None):
+        """forward_pair(rendered, masked) from the packed split-fp16 network input [B,H,W,8] that masking.demo_masked_image_packed wrote (channels 0-2
+        rendered, 3-5 masked, 6-7 zero): the same schedule without the pack step (smirk_generator_forward_packed, include/smirk_handoff.h), the same output
+        bits.  Inference in the split-fp16 mode only; no gradient flows into `packed`."""
+        L.raise_if_range_tripped("smirk_amd.SmirkGenerator.forward_packed")
+        if not self.accepts_packed():
+            raise L.SmirkHipError("smirk_amd.SmirkGenerator.forward_packed runs in eval mode with precision 'f16x3' and in_channels == 6 only "
+                                  "(training=%r, precision=%r, in_channels=%d)" % (self.training, self.precision, self.in_channels))
+        if packed.dim() != 4 or packed.shape[3] != 8:
+            raise L.SmirkHipError("expected the packed network input [B,H,W,8]")
+        B, H, W, _ = packed.shape
+        if H % 16 or W % 16:
+            raise L.SmirkHipError("input size must be a multiple of 16 (4 pooling levels; the reference's torch.cat of the skip tensors fails otherwise too)")
+        return self._enqueue(packed.device, B, H, W, _taps, [], lambda lib, w, out, tp, ws, nws, st: lib.smirk_generator_forward_packed(
+            w, L.ptr(packed), L.ptr(out), B, H, W, tp, L.ptr(ws, torch.uint8), nws, st))
 
     def _range_audit(self, taps, limit):
         """$SMIRK_F16X3_RANGE_CHECK=1 (or a limit): the split-fp16 format saturates at |x| = 65504 — BatchNorm'd activations of a trained network are
