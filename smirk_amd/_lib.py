@@ -355,6 +355,18 @@ def as_f32c(t):
     return t.contiguous()
 
 
+def aligned16(t):
+    """as_f32c on a 16-byte boundary: an offset view is cloned, because the kernels read 16-byte vectors"""
+    t = as_f32c(t)
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def second_backward(function, held):
+    """the error of a backward pass over a tape that the first one released"""
+    return RuntimeError(f"{function}.backward called a second time: the tape of {held} is released after the first backward pass "
+                        "(retain_graph=True is not supported by the HIP training path; run the forward again)")
+
+
 def profile_start():
     """Arm the library's launch profiler (include/smirk_hip.h): every kernel it launches from now on is bracketed by HIP events on its stream."""
     check(lib().smirk_profile_start())

@@ -31,7 +31,7 @@ Not built: recomputing the expand / depthwise activations inside a fused MBConv 
 import torch
 
 from . import _lib as L
-from .encoder_train import _EncOps, _pw_t, backbone_image, clamp_grad, head_forward, second_backward
+from .encoder_train import _EncOps, _pw_t, backbone_image, clamp_grad, head_forward
 
 
 class _EvalOps(_EncOps):
@@ -126,7 +126,7 @@ class BackboneEvalGradFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         if ctx.tape is None:
-            raise second_backward("BackboneEvalGradFunction", "activations")
+            raise L.second_backward("BackboneEvalGradFunction", "activations")
         tape = ctx.tape
         hw_, raw, n_exp, (B, hf, wf, Cf, N) = ctx.headrec
         ops = _EvalOps(raw.device, ctx.arith)

@@ -132,12 +132,6 @@ def clamp_grad(gout, raw, n_exp):
     return (gout * m).contiguous()
 
 
-def second_backward(function, held):
-    """the error of a backward pass over a tape that the first one released"""
-    return RuntimeError(f"{function}.backward called a second time: the tape of {held} is released after the first backward pass "
-                        "(retain_graph=True is not supported by the HIP training path; run the forward again)")
-
-
 def _pw(conv):
     """nn.Conv2d(cin, cout, 1) weight -> split16 [cout][cin]   (test helper; the step itself uses _EncOps.pack: both images in one launch)"""
     return _split16(conv.weight.detach().float().reshape(conv.out_channels, conv.in_channels).contiguous())
@@ -215,7 +209,7 @@ class BackboneTrainFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         if ctx.tape is None:
-            raise second_backward("BackboneTrainFunction", "raw convolution outputs")
+            raise L.second_backward("BackboneTrainFunction", "raw convolution outputs")
         backbone, head, tape = ctx.backbone, ctx.head, ctx.tape
         ctx.plan.check_tape(ctx.plan_generation, ctx.plan_versions)
         hw_, pooled, raw, n_exp, (B, hf, wf, Cf, N) = ctx.headrec

@@ -31,14 +31,13 @@ data gradients alone, with every BatchNorm scale folded into the data-gradient i
   pool, stem [2]        smirk_emotion_maxpool_backward_split16 with the stem's ReLU mask; smirk_emotion_stem_dgrad_split16, which also applies the upstream
                         gradient (per sample) and divides the lift out
 which is 2 + 6 * blocks + (blocks with a downsample) + (stride-2 blocks): 105 for [3, 4, 6, 3].  `launches(layers)` states both numbers.
-Arithmetic: f16x3 convolutions (fp32-class), fp32 elsewhere.
+The packed and folded weight images are the operands that frozen.FrozenNetwork caches (the rule is stated there).  Arithmetic: f16x3 convolutions (fp32-class), fp32 elsewhere.
 """
-import os
-
 import torch
 import torch.nn as nn
 
 from . import _lib as L
+from .frozen import FrozenNetwork, Holder, bn_affine, host64, image_pair, pack_conv, read_checkpoint
 from .smirk_generator import split16_to_float
 
 LAYERS = (3, 4, 6, 3)                                                  # resnet.py:160
@@ -50,16 +49,9 @@ FINAL = 7
 LIMIT_BYTES = 1 << 31
 
 
-class _Holder(nn.Module):
-    """A container of parameters in the reference's layout.  It is never called: the arithmetic is libsmirk_hip.so's."""
-
-    def forward(self, *a, **k):
-        raise L.SmirkHipError(f"{type(self).__name__} holds the parameters of smirk_amd.ExpressionLoss and has no forward of its own (no eager fallback "
-                              "exists): call ExpressionLoss")
-
-
-class Bottleneck(_Holder):
+class Bottleneck(Holder):
     """resnet.py:43-63 with emoca_specific=True on a stage's first block (the stride on conv2); the later blocks have stride 1, where the switch changes nothing."""
+    owner = "ExpressionLoss"
 
     def __init__(self, inplanes, planes, stride, downsample):
         super().__init__()
@@ -74,8 +66,9 @@ class Bottleneck(_Holder):
         self.stride = stride
 
 
-class ResNet(_Holder):
+class ResNet(Holder):
     """resnet.py:88-135 with Bottleneck blocks, num_classes=100, include_top=False (`fc` exists and is unused, as in the reference), emoca_specific=True."""
+    owner = "ExpressionLoss"
 
     def __init__(self, layers=LAYERS, num_classes=100):
         super().__init__()
@@ -114,22 +107,11 @@ def lift_of(metric, channels, hw=FINAL * FINAL):
     return float(1 << (n - 1).bit_length())
 
 
-# ---- host-side folding (plain torch, float64: runs without a device) ---------------------------------------------------------------------------------------
-def _host64(t):
-    return t.detach().cpu().double()
-
-
-def bn_affine(bn):
-    """BatchNorm in eval mode as y = x * s + t, float64 on the host."""
-    s = _host64(bn.weight) / torch.sqrt(_host64(bn.running_var) + bn.eps)
-    return s, _host64(bn.bias) - _host64(bn.running_mean) * s
-
-
 def fold_stem(conv, bn):
     """-> (forward image [64, 160]: k = (ky * 7 + kx) * 3 + c, zeros from 147 on; shift [64]; data-gradient image [7, 7, 3, 64]), float64, the BatchNorm scale
     folded into both images"""
     s, t = bn_affine(bn)
-    w = _host64(conv.weight) * s.view(-1, 1, 1, 1)                     # [co][c][ky][kx]
+    w = host64(conv.weight) * s.view(-1, 1, 1, 1)                     # [co][c][ky][kx]
     fwd = torch.zeros(w.shape[0], L.EMOTION_STEM_KPAD, dtype=torch.float64)
     fwd[:, :L.EMOTION_STEM_K] = w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)
     return fwd, t, w.permute(2, 3, 1, 0).contiguous()
@@ -191,8 +173,7 @@ class _Emotion(torch.autograd.Function):
         if not ctx.kept:
             return (None,) * 7
         if ctx.tape is None:
-            raise RuntimeError("ExpressionLoss: backward called a second time: the saved activations are released after the first backward pass "
-                               "(retain_graph=True is not supported by the HIP path; run the forward again)")
+            raise L.second_backward("ExpressionLoss", "saved activations")
         module, ops, stem, tape, pooled, aux, (B, H, W, hw, c), code, lift, use_mean = ctx.tape
         ctx.tape = None
         lib, st, dev, P = L.lib(), L.stream_ptr(), stem.device, L.ptr
@@ -237,63 +218,29 @@ class _Emotion(torch.autograd.Function):
         return None, dimg, None, None, None, None, None
 
 
-class ExpressionLoss(nn.Module):
+class ExpressionLoss(FrozenNetwork):
     """src/losses/ExpressionLoss.py.  `checkpoint`: a path or a dict in the reference's format ({'state_dict': {'backbone.*', 'linear.*'}}); None reads the
     reference's path (ExpressionLoss.py:32), relative to the working directory like there.  `layers`: the blocks per stage (the reference always uses
     (3, 4, 6, 3); shallower networks are for tests)."""
+    pin_eval = True                                                    # the running statistics whatever train() is called with (see the module docstring)
 
     def __init__(self, checkpoint=None, layers=LAYERS):
         super().__init__()
         self.backbone = ResNet(layers)
-        if checkpoint is None:
-            checkpoint = DEFAULT_CHECKPOINT
-        if not isinstance(checkpoint, dict):
-            path = os.fspath(checkpoint)
-            if not os.path.isfile(path):
-                raise FileNotFoundError(f"ExpressionLoss: `checkpoint` = {path!r} does not exist (the default is {DEFAULT_CHECKPOINT!r} relative to the working "
-                                        "directory, as in the reference; pass a path or a dict with 'state_dict')")
-            checkpoint = torch.load(path, map_location="cpu", weights_only=False)
-        load_reference_checkpoint(self, checkpoint)
-        for p in self.parameters():
-            p.requires_grad = False
-        super().train(False)
-        self._tensors = None                                           # every parameter and buffer the arithmetic reads (listed again after .to() / load_state_dict)
-        self._packed = None                                            # (key, operands)
+        load_reference_checkpoint(self, read_checkpoint(checkpoint, DEFAULT_CHECKPOINT, "ExpressionLoss", "'state_dict'", weights_only=False))
+        self.freeze()
 
-    def train(self, mode=True):
-        """The network is frozen and computes with the running statistics whatever `mode` is (see the module docstring); the layers stay in eval mode."""
-        return super().train(False)
+    def _reads(self, name):
+        return super()._reads(name) and not name.startswith("backbone.fc.")
 
-    def _apply(self, fn, *a, **k):
-        self._tensors = self._packed = None
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        self._tensors = self._packed = None
-        return super().load_state_dict(*a, **k)
-
-    def _operands(self, dev):
-        if self._tensors is None:
-            self._tensors = [t for n, t in list(self.named_parameters()) + list(self.named_buffers())
-                             if not n.endswith("num_batches_tracked") and not n.startswith("backbone.fc.")]
-        key = L.version_key(self._tensors)
-        if self._packed is not None and self._packed[0] == key:
-            return self._packed[1]
-        for t in self._tensors:
-            if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
-                raise L.SmirkHipError("ExpressionLoss: the parameters and buffers must be contiguous fp32 tensors on the images' device (call .to(device))")
-        lib, st = L.lib(), L.stream_ptr()
+    def _build_operands(self, dev):
         f32 = lambda v: v.float().contiguous().to(dev)
 
         def conv(m, bn):
             """-> ((forward image, epilogue scale, epilogue shift), data-gradient image of the convolution with the BatchNorm scale folded in)"""
             w = m.weight.detach()
-            cout, cin, kh = w.shape[0], w.shape[1], w.shape[2]
             s, t = bn_affine(bn)
-            folded = f32(_host64(w) * s.view(-1, 1, 1, 1))
-            fwd, dgrad = torch.empty(cout, kh * kh * cin, device=dev), torch.empty(cin, kh * kh * cout, device=dev)
-            L.check(lib.smirk_pack_conv_weights_split16(L.ptr(w), cout, cin, 0, cin, kh, cin, L.ptr(fwd), None, st))
-            L.check(lib.smirk_pack_conv_weights_split16(L.ptr(folded), cout, cin, 0, cin, kh, cin, None, L.ptr(dgrad), st))
+            fwd, dgrad = pack_conv(w, m.in_channels, dgrad_from=f32(host64(w) * s.view(-1, 1, 1, 1)))
             return (fwd, f32(s), f32(t)), dgrad
 
         net = self.backbone
@@ -306,23 +253,14 @@ class ExpressionLoss(nn.Module):
             if b.downsample is not None:
                 d["down"], d["down_d"] = conv(b.downsample[0], b.downsample[1])
             ops["blocks"].append(d)
-        self._packed = (key, ops)
         return ops
 
     def forward(self, gen, tar, use_mean=True, metric="l2", *, _trace=None):
         """gen, tar: [B, 3, H, W] fp32 on the HIP device, H and W in 193 .. 224 -> the loss, 0-dim with `use_mean` and [B] without, differentiable with respect
         to gen.  `_trace` (a dict) receives 'features' (fp32 [2B, 2048], gen rows first) and the decoded 'stem' output."""
-        for name, t in (("gen", gen), ("tar", tar)):
-            if not torch.is_tensor(t) or t.dim() != 4 or t.shape[1] != 3:
-                raise L.SmirkHipError(f"ExpressionLoss: {name} must be a [B, 3, H, W] tensor")
-            if not t.is_cuda:
-                raise L.SmirkHipError(f"smirk_amd runs on the MI355X HIP device only: ExpressionLoss: {name} is a CPU tensor (no CPU fallback exists)")
+        gc, tc = image_pair("ExpressionLoss", ("gen", "tar"), gen, tar)
         if metric not in L.EMOTION_METRICS:
             raise ValueError("Unknown metric {}".format(metric))      # ExpressionLoss.py:60
-        if tuple(gen.shape) != tuple(tar.shape) or gen.device != tar.device:
-            raise L.SmirkHipError(f"ExpressionLoss: gen {tuple(gen.shape)} and tar {tuple(tar.shape)} must have one shape and one device")
-        if tar.requires_grad:
-            raise L.SmirkHipError("ExpressionLoss: tar requires grad; the second image is the constant of the loss (smirk_trainer.py:117 passes the input image there)")
         B, _, H, W = gen.shape
         if B < 1 or not (MIN_SIZE <= H <= MAX_SIZE and MIN_SIZE <= W <= MAX_SIZE):
             raise L.SmirkHipError(f"ExpressionLoss: H and W must be {MIN_SIZE} .. {MAX_SIZE}, the sizes whose final map is {FINAL} x {FINAL} (the reference's "
@@ -332,9 +270,4 @@ class ExpressionLoss(nn.Module):
                                   "convolution entries; split the batch")
         L.raise_if_range_tripped("ExpressionLoss")
         keep = torch.is_grad_enabled() and gen.requires_grad
-        gc, tc = L.as_f32c(gen), L.as_f32c(tar.detach())
-        if gc.data_ptr() % 16:
-            gc = gc.clone()
-        if tc.data_ptr() % 16:
-            tc = tc.clone()
         return _Emotion.apply(self, gc, tc, metric, bool(use_mean), keep, _trace)

@@ -406,8 +406,7 @@ class GeneratorTrainFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         if ctx.tape is None:
-            raise RuntimeError("GeneratorTrainFunction.backward called a second time: the tape of raw convolution outputs is released after the first "
-                               "backward pass (retain_graph=True is not supported by the HIP training path; run the forward again)")
+            raise L.second_backward("GeneratorTrainFunction", "raw convolution outputs")
         module, tape, (d1, wf, y) = ctx.module, ctx.tape, ctx.final
         B, Cx, H, W = ctx.shape
         f = module.features

@@ -38,11 +38,6 @@ class Term:
         self.pred, self.target, self.flags, self.cols, self.weight, self.kind, self.loss_img = pred, target, flags, cols, float(weight), kind, bool(loss_img)
 
 
-def _aligned_f32(t):
-    t = L.as_f32c(t)
-    return t.clone() if t.data_ptr() % 16 else t                                       # an offset view: the kernels read 16-byte vectors
-
-
 def _prepare(terms):
     """Host-side validation and the fp32-contiguous, 16-byte aligned operands of every term.  Raises before anything touches the device."""
     terms = list(terms)
@@ -88,7 +83,7 @@ def _prepare(terms):
         if t.flags is not None:
             flags = t.flags.reshape(-1).contiguous()
             flags = flags.view(torch.uint8) if flags.dtype == torch.bool else flags
-        ops.append((_aligned_f32(t.pred.detach()), None if t.target is None else _aligned_f32(t.target), flags))
+        ops.append((L.aligned16(t.pred.detach()), None if t.target is None else L.aligned16(t.target), flags))
     return terms, ops
 
 

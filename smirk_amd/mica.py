@@ -22,18 +22,17 @@ One forward (all launches on the caller's stream, nothing waits for the host):
                         PReLU in place; [the downsample convolution of x with its BatchNorm in the epilogue;] conv2 with bn3 in the epilogue and the residual
   fc [2]                bn2, the flatten order and `features` folded into the matrix and the bias (fold_fc, float64 on the host); smirk_mica_fc_split16
   head [1]              smirk_mica_head: F.normalize and the five Linear layers
-Packed weights, folded scales / shifts, the folded FC matrix and the head blob are cached under (data_ptr, _version) of every parameter and buffer and rebuilt
-into fresh buffers when one moves (that rebuild reads the parameters on the host: it is the only step that waits).  Batches above 64 run in chunks of at
-most 64.  Arithmetic: f16x3 convolutions (fp32-class), fp32 elsewhere.
+Packed weights, folded scales / shifts, the folded FC matrix and the head blob are the operands that frozen.FrozenNetwork caches (the rule is stated there).
+Batches above 64 run in chunks of at most 64.  Arithmetic: f16x3 convolutions (fp32-class), fp32 elsewhere.
 """
 import ctypes as C
 import math
-import os
 
 import torch
 import torch.nn as nn
 
 from . import _lib as L
+from .frozen import FrozenNetwork, Holder, bn_affine, device_image, host64, pack_conv, read_checkpoint
 from .losses import Term, weighted_loss
 
 LAYERS = (3, 13, 30, 3)                                               # arcface.py:166
@@ -47,15 +46,9 @@ def kaiming_leaky_init(m):
         torch.nn.init.kaiming_normal_(m.weight, a=0.2, mode="fan_in", nonlinearity="leaky_relu")
 
 
-class _Holder(nn.Module):
-    """A container of parameters in the reference's layout.  It is never called: the arithmetic is libsmirk_hip.so's."""
-
-    def forward(self, *a, **k):
-        raise L.SmirkHipError(f"{type(self).__name__} holds the parameters of smirk_amd.MICA and has no forward of its own (no eager fallback exists): call MICA")
-
-
-class MappingNetwork(_Holder):
+class MappingNetwork(Holder):
     """mica.py:14-43: `network` (1 + hidden Linear layers, leaky_relu(0.2) after each) and `output`.  MICA runs it inside its fused head kernel."""
+    owner = "MICA"
 
     def __init__(self, z_dim, map_hidden_dim, map_output_dim, hidden=2):
         super().__init__()
@@ -71,7 +64,9 @@ class MappingNetwork(_Holder):
         return list(self.network) + [self.output]
 
 
-class IBasicBlock(_Holder):
+class IBasicBlock(Holder):
+    owner = "MICA"
+
     def __init__(self, inplanes, planes, stride, downsample):
         super().__init__()
         self.bn1 = nn.BatchNorm2d(inplanes, eps=1e-05)
@@ -84,8 +79,9 @@ class IBasicBlock(_Holder):
         self.stride = stride
 
 
-class Arcface(_Holder):
+class Arcface(Holder):
     """arcface.py:65-198 with `layers` blocks per stage (the reference: [3, 13, 30, 3])."""
+    owner = "MICA"
 
     def __init__(self, layers=LAYERS):
         super().__init__()
@@ -108,25 +104,14 @@ class Arcface(_Holder):
         return [b for k in range(4) for b in getattr(self, f"layer{k + 1}")]
 
 
-# ---- host-side folding (plain torch, float64: runs without a device) ---------------------------------------------------------------------------------------
-def _host64(t):
-    return t.detach().cpu().double()
-
-
-def bn_affine(bn):
-    """BatchNorm in eval mode as y = x * s + t, float64 on the host."""
-    s = _host64(bn.weight) / torch.sqrt(_host64(bn.running_var) + bn.eps)
-    return s, _host64(bn.bias) - _host64(bn.running_mean) * s
-
-
 def fold_fc(fc, bn2, features, hw):
     """features(fc(flatten_nchw(bn2(x)))) as x_nhwc_flat @ w'.T + b' (float64): w'[n][k'] = g[n] w[n][k] s[c], b'[n] = g[n] (b[n] + sum_k w[n][k] t[c]) + h[n]
     with k = c * hw + p the reference's flatten index and k' = p * C + c its NHWC position."""
     s, t = bn_affine(bn2)
     g, h = bn_affine(features)
     n, c = fc.out_features, s.numel()
-    w = _host64(fc.weight).view(n, c, hw)
-    bias = g * (_host64(fc.bias) + (w * t.view(1, c, 1)).sum((1, 2))) + h
+    w = host64(fc.weight).view(n, c, hw)
+    bias = g * (host64(fc.bias) + (w * t.view(1, c, 1)).sum((1, 2))) + h
     w = (g.view(n, 1, 1) * w * s.view(1, c, 1)).permute(0, 2, 1).reshape(n, hw * c)
     return w.contiguous(), bias
 
@@ -140,41 +125,18 @@ def load_reference_checkpoint(module, checkpoint):
     module.regressor.load_state_dict({k.replace("regressor.", ""): v for k, v in checkpoint["flameModel"].items() if "network" in k or "output" in k}, strict=True)
 
 
-class MICA(nn.Module):
+class MICA(FrozenNetwork):
     """src/models/MICA/mica.py:48-94.  `checkpoint`: a path or a dict in the reference's format; None reads assets/mica.tar like the reference.  `layers`: the
     blocks per stage (the reference always uses (3, 13, 30, 3); shallower networks are for tests)."""
+    pin_eval = True                                                    # the running statistics whatever train() is called with (see the module docstring)
 
     def __init__(self, checkpoint=None, layers=LAYERS):
         super().__init__()
         self.arcface = Arcface(layers)
         self.regressor = MappingNetwork(512, 300, 300, hidden=3)
-        if checkpoint is None:
-            checkpoint = DEFAULT_CHECKPOINT
-        if not isinstance(checkpoint, dict):
-            path = os.fspath(checkpoint)
-            if not os.path.isfile(path):
-                raise FileNotFoundError(f"MICA: `checkpoint` = {path!r} does not exist (the default is {DEFAULT_CHECKPOINT!r} relative to the working directory, "
-                                        "as in the reference; pass a path or a dict with 'arcface' and 'flameModel')")
-            checkpoint = torch.load(path, map_location="cpu")
-        load_reference_checkpoint(self, checkpoint)
-        for p in self.parameters():
-            p.requires_grad = False
-        super().train(False)
+        load_reference_checkpoint(self, read_checkpoint(checkpoint, DEFAULT_CHECKPOINT, "MICA", "'arcface' and 'flameModel'"))
+        self.freeze()
         self._ws = L.Workspace()
-        self._tensors = None                                           # every parameter and buffer the arithmetic reads (listed again after .to() / load_state_dict)
-        self._packed = None                                            # (key, operands)
-
-    def train(self, mode=True):
-        """The network is frozen and computes with the running statistics whatever `mode` is (see the module docstring); the layers stay in eval mode."""
-        return super().train(False)
-
-    def _apply(self, fn, *a, **k):
-        self._tensors = self._packed = None
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        self._tensors = self._packed = None
-        return super().load_state_dict(*a, **k)
 
     @property
     def image_size(self):
@@ -182,26 +144,12 @@ class MICA(nn.Module):
         return 16 * math.isqrt(self.arcface.fc.in_features // 512)
 
     # ---- operands ----------------------------------------------------------------------------------------------------------------------------------------
-    def _operands(self, dev):
-        if self._tensors is None:
-            self._tensors = [t for n, t in list(self.named_parameters()) + list(self.named_buffers()) if not n.endswith("num_batches_tracked")]
-        key = L.version_key(self._tensors)
-        if self._packed is not None and self._packed[0] == key:
-            return self._packed[1]
-        for t in self._tensors:
-            if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
-                raise L.SmirkHipError("MICA: the parameters and buffers must be contiguous fp32 tensors on the images' device (call .to(device))")
-        lib, st = L.lib(), L.stream_ptr()
+    def _build_operands(self, dev):
         f32 = lambda v: v.float().to(dev)
 
         def conv(m, bn):                                               # (packed split16 weight, epilogue scale, epilogue shift) of a convolution and the BatchNorm behind it
-            w = m.weight.detach()
-            cout, cin, kh = w.shape[0], w.shape[1], w.shape[2]
-            cp = max(cin, 8)
-            packed = torch.empty(cout, kh * kh * cp, device=dev)
-            L.check(lib.smirk_pack_conv_weights_split16(L.ptr(w), cout, cin, 0, cin, kh, cp, L.ptr(packed), None, st))
             s, t = bn_affine(bn)
-            return packed, f32(s), f32(t)
+            return pack_conv(m.weight.detach(), max(m.in_channels, 8))[0], f32(s), f32(t)
 
         a = self.arcface
         ops = {"stem": conv(a.conv1, a.bn1) + (a.prelu.weight.detach(),), "blocks": []}
@@ -225,7 +173,6 @@ class MICA(nn.Module):
                 off += pad4(t.numel())
             head.layer[k].n_in, head.layer[k].n_out = m.in_features, m.out_features
         ops["head"], ops["head_blob"], ops["n_out"] = head, blob, lin[-1].out_features
-        self._packed = (key, ops)
         return ops
 
     # ---- the schedule --------------------------------------------------------------------------------------------------------------------------------------
@@ -263,19 +210,13 @@ class MICA(nn.Module):
         return feat, out
 
     def _run(self, images):
-        if not torch.is_tensor(images) or images.dim() != 4 or images.shape[1] != 3:
-            raise L.SmirkHipError("MICA: images must be a [B, 3, H, W] tensor")
-        if not images.is_cuda:
-            raise L.SmirkHipError("smirk_amd runs on the MI355X HIP device only: MICA: images is a CPU tensor (no CPU fallback exists)")
+        img = device_image("MICA", "images", images)
         s = self.image_size
         if images.shape[0] < 1 or tuple(images.shape[2:]) != (s, s):
             raise L.SmirkHipError(f"MICA: images must be [B >= 1, 3, {s}, {s}] (the size fc.in_features = {self.arcface.fc.in_features} implies), got {tuple(images.shape)}")
         if images.requires_grad:
             raise L.SmirkHipError("MICA: images requires grad; the network is forward-only (the reference never differentiates through MICA: mica.py:84-86)")
         L.raise_if_range_tripped("MICA")
-        img = L.as_f32c(images.detach())
-        if img.data_ptr() % 16:
-            img = img.clone()
         ops = self._operands(img.device)
         parts = [self._chunk(img[i:i + MAX_CHUNK], ops) for i in range(0, img.shape[0], MAX_CHUNK)]
         return parts[0] if len(parts) == 1 else tuple(torch.cat(p) for p in zip(*parts))

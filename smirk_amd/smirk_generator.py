@@ -43,6 +43,7 @@ class ResnetBlock(nn.Module):
 
 
 def _bn_affine(bn):
+    # fp32 on the device, on purpose: it must not wait for the host.  Not frozen.bn_affine, the float64 host fold of the frozen networks.
     scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
     return scale.contiguous(), (bn.bias.detach().float() - bn.running_mean.detach().float() * scale).contiguous()
 

@@ -13,7 +13,8 @@ and `std`), so the reference's state dicts load; the layers themselves are never
 into one split16 NHWC tensor [2B, H, W, 8] (csrc/vgg_loss.hip), the ten convolutions run on smirk_conv_igemm_f16x3 (shift = bias, fused ReLU) over the 2B
 rows, each tap leaves float64 partial sums, and one finalise launch turns them into the four terms and their total.  The weights are frozen, so the
 backward is data gradients only, over the x rows alone: tap / ReLU kernel, the same convolution entry with the rotated weights, the pool backward, and the
-backward of the packing.  No launch waits for the host.  Arithmetic: f16x3 (fp32-class).
+backward of the packing.  No launch waits for the host.  The packed weight images are the operands that frozen.FrozenNetwork caches (the rule is stated
+there).  Arithmetic: f16x3 (fp32-class).
 """
 import ctypes as C
 from collections import OrderedDict
@@ -23,6 +24,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib as L
+from .frozen import FrozenNetwork, image_pair, pack_conv
 from .smirk_generator import split16_to_float
 
 CHANNELS = (64, 64, 128, 128, 256, 256, 256, 512, 512, 512)           # output channels of the ten convolutions
@@ -113,8 +115,7 @@ class _VGGLoss(torch.autograd.Function):
         if not ctx.kept:
             return None, None, None, None, None
         if ctx.tape is None:
-            raise RuntimeError("VGGPerceptualLoss: backward called a second time: the saved activations are released after the first backward pass "
-                               "(retain_graph=True is not supported by the HIP path; run the forward again)")
+            raise L.second_backward("VGGPerceptualLoss", "saved activations")
         module, relu_x, tap_full, wd, (B, H, W), scale = ctx.tape
         ctx.tape = None
         lib, st, dev = L.lib(), L.stream_ptr(), relu_x[0].device
@@ -138,7 +139,7 @@ class _VGGLoss(torch.autograd.Function):
         return None, dx, None, None, None
 
 
-class VGGPerceptualLoss(nn.Module):
+class VGGPerceptualLoss(FrozenNetwork):
     """src/losses/VGGPerceptualLoss.py.  `features`: None (torchvision's pretrained vgg16, imported lazily, as the reference does), an nn.Sequential with
     torchvision's layout, or a list of ten (weight, bias) pairs.  `resize_to`: the size both images are resized to (the reference: 224 x 224); None runs the
     network at the input's own size.  The parameters are frozen like the reference's (:15-17)."""
@@ -166,13 +167,11 @@ class VGGPerceptualLoss(nn.Module):
         for idx in (4, 9, 16):
             if not isinstance(self._layer(idx), nn.MaxPool2d):
                 raise L.SmirkHipError(f"VGGPerceptualLoss: features[{idx}] must be MaxPool2d(2, 2), got {self._layer(idx)}")
-        for p in self.blocks.parameters():
-            p.requires_grad = False
+        self.freeze()
         self.register_buffer("mean", torch.tensor(MEAN).view(1, 3, 1, 1))
         self.register_buffer("std", torch.tensor(STD).view(1, 3, 1, 1))
         self.resize_to = None if resize_to is None else (int(resize_to[0]), int(resize_to[1]))
         self._ws = L.Workspace()
-        self._packed = {}                                                # conv ordinal -> ((data_ptr, _version), forward image, data-gradient image)
 
     def _layer(self, idx):
         for (lo, hi), b in zip(BLOCK_SLICES, self.blocks):
@@ -183,45 +182,21 @@ class VGGPerceptualLoss(nn.Module):
     def convs(self):
         return [self._layer(i) for i in CONV_INDEX]
 
-    def _operands(self, dev):
-        """The split16 operand images of the ten weights, forward [Cout][(ky,kx,c)] and data-gradient [cin_pad][(ky,kx,co)], and the biases.  Packed once; a
-        weight is packed again only when its data_ptr or its version counter moved (into fresh buffers: an earlier forward's tape keeps the images it ran with)."""
-        lib, st = L.lib(), L.stream_ptr()
-        wf, wd, bias = [], [], []
-        for k, conv in enumerate(self.convs()):
-            w, b = conv.weight, conv.bias
-            if w.device != dev or b.device != dev or w.dtype != torch.float32 or b.dtype != torch.float32 or not w.is_contiguous() or not b.is_contiguous():
-                raise L.SmirkHipError("VGGPerceptualLoss: the weights must be contiguous fp32 tensors on the inputs' device (call .to(device))")
-            key = (w.data_ptr(), w._version)
-            hit = self._packed.get(k)
-            if hit is None or hit[0] != key:
-                cout, cin = w.shape[0], w.shape[1]
-                cp = max(cin, 8)
-                f, d = torch.empty(cout, 9 * cp, device=dev), torch.empty(cp, 9 * cout, device=dev)
-                L.check(lib.smirk_pack_conv_weights_split16(L.ptr(w.detach()), cout, cin, 0, cin, 3, cp, L.ptr(f), L.ptr(d), st))
-                hit = self._packed[k] = (key, f, d)
-            wf.append(hit[1])
-            wd.append(hit[2])
-            bias.append(b.detach())
-        return wf, wd, bias
+    def _build_operands(self, dev):
+        """-> (wf, wd, bias): the split16 operand images of the ten weights, forward [Cout][(ky,kx,c)] and data-gradient [cin_pad][(ky,kx,co)], and the biases
+        (live views of the parameters)"""
+        packed = [pack_conv(c.weight.detach(), max(c.in_channels, 8), dgrad=True) for c in self.convs()]
+        return [f for f, _ in packed], [d for _, d in packed], [c.bias.detach() for c in self.convs()]
 
     def forward(self, x, y, *, _trace=None):
         """x, y: [B, 3, H, W] fp32 on the HIP device -> the 0-dim fp32 loss, differentiable with respect to x.  `_trace` (a dict) receives the decoded fp32
         NCHW activations 'relu_x' (the ten ReLU outputs of the x rows) and 'tap_y' (the four tap features of the y rows), and the four 'terms'."""
-        for name, t in (("x", x), ("y", y)):
-            if not torch.is_tensor(t) or t.dim() != 4 or t.shape[1] != 3:
-                raise L.SmirkHipError(f"VGGPerceptualLoss: {name} must be a [B, 3, H, W] tensor")
-            if not t.is_cuda:
-                raise L.SmirkHipError(f"smirk_amd runs on the MI355X HIP device only: VGGPerceptualLoss: {name} is a CPU tensor (no CPU fallback exists)")
-        if tuple(x.shape) != tuple(y.shape) or x.device != y.device:
-            raise L.SmirkHipError(f"VGGPerceptualLoss: x {tuple(x.shape)} and y {tuple(y.shape)} must have one shape and one device")
-        if y.requires_grad:
-            raise L.SmirkHipError("VGGPerceptualLoss: y requires grad; the second image is the constant of the loss (smirk_trainer.py:104 passes the input image there)")
+        x, y = image_pair("VGGPerceptualLoss", ("x", "y"), x, y)
         if self.resize_to is not None and tuple(x.shape[2:]) != self.resize_to:
             # off the hot path (the trainer's images are 224 x 224): eager torch, differentiable.  The resize is a convex combination per pixel, so it commutes
-            # with the per-channel affine map that the packing kernel applies afterwards.
-            x = F.interpolate(x.float(), mode="bilinear", size=self.resize_to, align_corners=False)
-            y = F.interpolate(y.float(), mode="bilinear", size=self.resize_to, align_corners=False)
+            # with the per-channel affine map that the packing kernel applies afterwards.  Its outputs are fresh fp32 contiguous tensors: still conditioned.
+            x = F.interpolate(x, mode="bilinear", size=self.resize_to, align_corners=False)
+            y = F.interpolate(y, mode="bilinear", size=self.resize_to, align_corners=False)
         B, _, H, W = x.shape
         if B < 1 or H % 8 or W % 8 or H < 16 or W < 16:
             raise L.SmirkHipError(f"VGGPerceptualLoss: the network needs H and W to be multiples of 8 and at least 16 (three 2 x 2 pools), got {H} x {W}")
@@ -230,9 +205,4 @@ class VGGPerceptualLoss(nn.Module):
                                   "split the batch")
         L.raise_if_range_tripped("VGGPerceptualLoss")
         keep = torch.is_grad_enabled() and x.requires_grad
-        xc, yc = L.as_f32c(x), L.as_f32c(y.detach())
-        if xc.data_ptr() % 16:
-            xc = xc.clone()
-        if yc.data_ptr() % 16:
-            yc = yc.clone()
-        return _VGGLoss.apply(self, xc, yc, keep, _trace)[0]
+        return _VGGLoss.apply(self, x, y, keep, _trace)[0]

@@ -340,8 +340,8 @@ def test_a_weight_changed_in_place_is_packed_again():
     mod = VGGPerceptualLoss(synth_weights(1), resize_to=None).cuda()
     a = mod(c["x"], c["y"])
     assert torch.equal(a, c["loss"])
-    packed = {k: v[1].data_ptr() for k, v in mod._packed.items()}
-    assert torch.equal(mod(c["x"], c["y"]), a) and packed == {k: v[1].data_ptr() for k, v in mod._packed.items()}      # unchanged weights: packed once
+    packed = [f.data_ptr() for f in mod._packed[1][0]]                                                    # the ten forward images of the frame's (key, (wf, wd, bias))
+    assert torch.equal(mod(c["x"], c["y"]), a) and packed == [f.data_ptr() for f in mod._packed[1][0]]      # unchanged weights: packed once
     with torch.no_grad():
         mod.convs()[9].weight.mul_(2.0)
     b = mod(c["x"], c["y"])
