@@ -144,6 +144,20 @@ int smirk_conv3x3_patch_launch(const SmirkConvDesc* d, const void* in0, const vo
 #define HS_WGM 4
 bool smirk_conv_halo_eligible(const ConvArgs& a);
 int smirk_conv_halo_launch(const ConvArgs& a, hipStream_t st, bool x1);
+// conv_halo.hip: decoder levels with c = 128 / 256 output channels (split-fp16 only), ConvTranspose2d(2c -> c, k2 s2) composed into the level's first 3x3 convolution as
+// TWO launches: conv_halo_up_kernel (2 x 2 coarse taps per output parity class -> partial', stored at the fine pixels) and the ordinary 3x3 convolution over the skip
+// tensor with partial' as its residual.  smirk_updeep_compose rebuilds weff / shift16 / wskip of up to two levels in ONE launch, once per forward.
+struct SmirkUpdeepLevel {
+    int c;                                  // output channels of the level
+    const SmirkConvLayer *up, *conv;        // the ConvTranspose2d layer (shift = bias) and the first 3x3 layer over cat(up, skip) with its folded BatchNorm
+    void *weff, *shift16, *wskip;           // workspace of smirk_updeep_{weff,shift,wskip}_bytes(c)
+};
+size_t smirk_updeep_weff_bytes(int c);
+size_t smirk_updeep_shift_bytes(int c);
+size_t smirk_updeep_wskip_bytes(int c);
+bool smirk_updeep_eligible(int B, int H, int W, int c);                 // H x W: the FINE image; both launches pass smirk_conv_halo_eligible with their own M
+int smirk_updeep_compose(const SmirkUpdeepLevel* lv, int nlv, hipStream_t st);
+int smirk_updeep_coarse_launch(const SmirkUpdeepLevel* lv, const void* d, void* partial, int B, int H, int W, hipStream_t st);
 // conv_pp.hip: 8-wave ping-pong kernel (256 x 128 tile, 3-stage ring) for the deep split-fp16 3x3 layers
 bool smirk_conv_pp_eligible(const ConvArgs& a);
 int smirk_conv_pp_launch(const ConvArgs& a, hipStream_t st);

@@ -35,8 +35,9 @@ template <int K>
 using hs_ic = std::integral_constant<int, K>;
 
 // byte offset inside the B ring of (row, stage, 16-byte piece): blocks of 8 rows, the three stages of a block adjacent (conv_pp.hip)
+template <int NST = HS_NSTAGE>
 __device__ __forceinline__ int hs_b_off(int row, int stage, int piece) {
-    return ((((row >> 3) * HS_NSTAGE + stage) << 8) + ((row & 7) << 5) + ((piece ^ ((row >> 1) & 7)) << 2)) * 4;
+    return ((((row >> 3) * NST + stage) << 8) + ((row & 7) << 5) + ((piece ^ ((row >> 1) & 7)) << 2)) * 4;
 }
 
 // NPA: halo pieces (1 KiB = 8 pixel rows of 128 B) per wave and channel chunk; the halo buffer holds 64 NPA rows >= 256 + 2 (W + 1)
@@ -46,39 +47,50 @@ __device__ __forceinline__ int hs_b_off(int row, int stage, int piece) {
 //      pipe busy while the partner wakes up.  Nothing the barrier orders depends on the position of a wave's MFMAs (they only touch registers).
 // X1:  one fp16 MFMA per product block on the hi halves only (the training path's "f16x1" arithmetic, generator_train.TRAIN_ARITH): the lo fragments are neither
 //      read from LDS nor multiplied — 8 of the 24 MFMAs and 8 of the 16 fragment reads of a chunk remain.  Same K order as conv_igemm_kernel's X1 instantiation.
-template <int NPA, int EB, bool X1, bool STATS = false>
+// UP:  the coarse half of a decoder level whose ConvTranspose2d(k2 s2) is composed into the 3x3 convolution that reads it: GEMM rows are COARSE
+//      raster pixels of ONE output parity class (dy, dx) (the class comes from the grid), K walks channel chunks x the class's 2 x 2 coarse taps
+//      {dy-1, dy} x {dx-1, dx}, the weights are Weff[class] (ordinary conv rows [N][4 Cin]), the halo is the 256 + W + 1 consecutive pixels from the class's first
+//      tap on (5 pieces for every W <= 63).  Four taps per chunk: the B ring has FOUR stages so that a tap's stage stays a compile-time constant.  Epilogue:
+//      scale, the shift row of (class, row edge, column edge), no activation, stored at the FINE pixel (2y + dy, 2x + dx).
+//      LDS: 64 KB ring + 2 x (40 KB + 128 B) halo = 147,712 B; 234 VGPRs, no scratch (-Rpass-analysis=kernel-resource-usage).
+template <int NPA, int EB, bool X1, bool STATS = false, bool UP = false>
 __device__ __forceinline__ void conv_halo_body(const ConvArgs& a) {
-    constexpr int NL = 3;   // DMA instructions issued in the load phase: 1-3 measured equal, 0 (all among the MFMAs) 2-3 % slower (profiles/r03b_halo_nl_sweep.txt)
+    constexpr int NTAP = UP ? 4 : 9, NST = UP ? 4 : HS_NSTAGE;
+    constexpr int NL = UP ? 4 : 3;   // DMA instructions issued in the load phase: 1-3 measured equal, 0 (all among the MFMAs) 2-3 % slower (profiles/r03b_halo_nl_sweep.txt)
     extern __shared__ __attribute__((aligned(16))) float hs_smem[];
     char* lds = (char*)hs_smem;
     constexpr int ABUF = NPA * 8 * 1024;                            // one halo buffer
     constexpr int ASTRIDE = ABUF + 128;                             // + its row of zeros (byte offset ABUF inside the buffer)
-    constexpr int A0 = HS_BRING_BYTES;                              // halo buffer u starts at A0 + u * ASTRIDE
+    constexpr int A0 = NST * HS_BN * 128;                               // halo buffer u starts at A0 + u * ASTRIDE
     const SmirkConvDesc& d = a.d;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int swave = __builtin_amdgcn_readfirstlane(wave);
     const int wm = wave >> 1, wn = wave & 1;                       // 4 (M) x 2 (N) waves of 64 x 64
     const int group = swave >> 2;                                    // 0: leads, 1: one phase behind (shares each SIMD with a wave of group 0)
     const int ntn = a.N / HS_BN;
-    const int logical = xcd_logical(blockIdx.x, gridDim.x);
+    int logical = xcd_logical(blockIdx.x, gridDim.x);
+    int cls = 0;                                                     // UP: the grid is 4 classes x tiles, a class's tiles adjacent (they share Weff[class] in L2)
+    if constexpr (UP) { const int ntile = (int)gridDim.x >> 2; cls = logical / ntile; logical -= cls * ntile; }
+    const int dyc = cls >> 1, dxc = cls & 1;
     const int m0 = (logical / ntn) * HS_BM, n0 = (logical % ntn) * HS_BN;
     const int W = d.W, HW = d.H * d.W;
+    const float* const wcls = UP ? a.w + (size_t)cls * a.N * a.K : a.w;
     const int fr = lane & 31, hb = lane >> 5;
 
     // ---- zero rows (read by every tap that falls into the zero padding) ------------------------------------------------------------------------
     if (tid < 64) *(float*)(lds + A0 + (tid >> 5) * ASTRIDE + ABUF + (tid & 31) * 4) = 0.f;
 
-    unsigned tabA[9];                                              // per-lane tap table, filled in the prologue while the first DMAs fly
+    unsigned tabA[NTAP];                                              // per-lane tap table, filled in the prologue while the first DMAs fly
     // B fragment bases: (k-step 0, hi) piece of rows (wn*2 + j)*32 + fr in stage 0
     unsigned bB[2];
 #pragma unroll
-    for (int j = 0; j < 2; ++j) bB[j] = (unsigned)hs_b_off((wn * 2 + j) * 32 + fr, 0, 2 * hb);
+    for (int j = 0; j < 2; ++j) bB[j] = (unsigned)hs_b_off<NST>((wn * 2 + j) * 32 + fr, 0, 2 * hb);
 
     // ---- DMA coordinates ------------------------------------------------------------------------------------------------------------------------
     const int pos = lane & 7, lrow = lane >> 3;                    // a wave-wide LDS-DMA writes 8 rows x 8 pieces lane-linearly
     // halo piece k of this wave = block swave + 8k = halo rows 8 (swave + 8k) + lrow; (row >> 1) & 7 does not depend on k
     const unsigned colA16 = (unsigned)(pos ^ ((4 * (swave & 1) + (lrow >> 1)) & 7)) * 16u;
-    const int qv0 = m0 - (W + 1) + 8 * swave + lrow;                // linear pixel of piece 0's row (may be negative / beyond the tensor)
+    const int qv0 = m0 + (UP ? (dyc - 1) * W + (dxc - 1) : -(W + 1)) + 8 * swave + lrow;                // linear pixel of piece 0's row (may be negative / beyond the tensor)
     const int npix = d.B * HW;
     unsigned voffB[2];
 #pragma unroll
@@ -89,7 +101,7 @@ __device__ __forceinline__ void conv_halo_body(const ConvArgs& a) {
     const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc((void*)a.in0, (short)0, (int)((long long)npix * d.C0 * 4), 0x00020000);
     const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)(d.C1 > 0 ? a.in1 : a.in0), (short)0,
                                                                          (int)((long long)npix * (d.C1 > 0 ? d.C1 : d.C0) * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, (short)0, (int)((long long)a.N * a.K * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)wcls, (short)0, (int)((long long)a.N * a.K * 4), 0x00020000);
     const int sh0 = 31 - __builtin_clz((unsigned)d.C0) + 2, sh1 = d.C1 > 0 ? 31 - __builtin_clz((unsigned)d.C1) + 2 : sh0;
     const int ncc = (d.C0 + d.C1) / CV_BK;
 
@@ -110,7 +122,7 @@ __device__ __forceinline__ void conv_halo_body(const ConvArgs& a) {
     auto dmaB1 = [&](int cc, auto tapc, auto stc, auto pc) {
         constexpr int TAP = decltype(tapc)::value, ST = decltype(stc)::value, P = decltype(pc)::value;
         const int so = (TAP * a.Cin + cc * CV_BK) * 4;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (hs_lptr_t)(lds + (((swave + 8 * P) * HS_NSTAGE + ST) << 10)), 16, voffB[P], so, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (hs_lptr_t)(lds + (((swave + 8 * P) * NST + ST) << 10)), 16, voffB[P], so, 0, 0);
     };
     auto dmaB = [&](int cc, auto tapc, auto stc) {
         dmaB1(cc, tapc, stc, hs_ic<0>{});
@@ -128,7 +140,7 @@ __device__ __forceinline__ void conv_halo_body(const ConvArgs& a) {
 
     // one (load phase, matrix phase) pair for chunk (cc, TAP): A from the halo buffer at `acur`, B from ring stage TAP % 3
     auto body = [&](int cc, int acur, int anext, auto tapc) {
-        constexpr int TAP = decltype(tapc)::value, ST = TAP % 3;
+        constexpr int TAP = decltype(tapc)::value, ST = TAP % NST;
         // ---- load phase ------------------------------------------------------------------------------------------------------------------------
         {
             const unsigned t = tabA[TAP];
@@ -154,20 +166,24 @@ __device__ __forceinline__ void conv_halo_body(const ConvArgs& a) {
         }
         // this phase pair's DMA list: [halo piece TAP of the NEXT channel chunk (taps 0 .. NPA-1),] the two weight pieces of the chunk two ahead.  Past
         // the end of K the clamped last chunk is fetched again into a buffer / stage nobody reads: no branch in the loop bodies.
-        constexpr int T2 = (TAP + 2) % 9;
-        constexpr int HASA = TAP < NPA ? 1 : 0, NDMA = 2 + HASA, NLD = NL < NDMA ? NL : NDMA;
-        const int ccA = min(cc + 1, ncc - 1), ccB = min(cc + (TAP + 2 >= 9 ? 1 : 0), ncc - 1);
+        // (UP: a piece issued in phase q by a wave of the trailing group is only known to have landed when the leading group enters phase q + 2, so the next
+        // chunk's halo must be out by tap 2 of 4: tap t < 3 issues pieces t and t + 3, NPA <= 6)
+        constexpr int T2 = (TAP + 2) % NTAP;
+        constexpr int HASA = UP ? (TAP < 3 ? 1 + (TAP + 3 < NPA ? 1 : 0) : 0) : (TAP < NPA ? 1 : 0), NDMA = 2 + HASA, NLD = NL < NDMA ? NL : NDMA;
+        const int ccA = min(cc + 1, ncc - 1), ccB = min(cc + (TAP + 2 >= NTAP ? 1 : 0), ncc - 1);
         auto dma = [&](auto kc) {                                    // DMA instruction K of the list
             constexpr int K = decltype(kc)::value;
-            if constexpr (HASA && K == 0) dmaA(ccA, anext, hs_ic<(TAP < NPA ? TAP : 0)>{});
-            else dmaB1(ccB, hs_ic<T2>{}, hs_ic<T2 % 3>{}, hs_ic<K - HASA>{});
+            if constexpr (K < HASA) dmaA(ccA, anext, hs_ic<(TAP + 3 * K < NPA ? TAP + 3 * K : 0)>{});
+            else dmaB1(ccB, hs_ic<T2>{}, hs_ic<T2 % NST>{}, hs_ic<(K - HASA) & 1>{});
         };
         if constexpr (NLD > 0) dma(hs_ic<0>{});
         if constexpr (NLD > 1) dma(hs_ic<1>{});
         if constexpr (NLD > 2) dma(hs_ic<2>{});
+        if constexpr (NLD > 3) dma(hs_ic<3>{});
         // everything older than this load phase's DMA instructions has landed (this wave's share of chunk q+1's weights, and every halo piece issued
         // in an earlier phase); fragment reads done
-        if constexpr (NLD == 3) asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)" ::: "memory");
+        if constexpr (NLD == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
+        else if constexpr (NLD == 3) asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)" ::: "memory");
         else if constexpr (NLD == 2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
         else if constexpr (NLD == 1) asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -229,14 +245,21 @@ __device__ __forceinline__ void conv_halo_body(const ConvArgs& a) {
     // ---- per-lane tap table: LDS byte offset (inside a halo buffer) of the (k-step 0, hi) piece of this lane's A row for each tap; rows i = 0 / 1
     //      of the wave tile in the low / high 16 bits.  The other three pieces of a row are offset ^ 16 (lo), ^ 64 (k-step 1), ^ 80. --------------
     {
-        unsigned ent[2][9];
+        unsigned ent[2][NTAP];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int rl = (wm * 2 + i) * 32 + fr;
             const int m = m0 + rl;
             const int b = m / HW, rem = m - b * HW, y = rem / W, x = rem - y * W;
 #pragma unroll
-            for (int t = 0; t < 9; ++t) {
+            for (int t = 0; t < NTAP; ++t) {
+                if constexpr (UP) {                               // tap (ta, tb) reads coarse pixel (y + dy - 1 + ta, x + dx - 1 + tb) = halo row rl + ta W + tb
+                    const int ta = t >> 1, tb = t & 1, ay = y + dyc - 1 + ta, ax = x + dxc - 1 + tb;
+                    const bool zero = m >= a.M || ay < 0 || ay >= d.H || ax < 0 || ax >= W;
+                    const int p = rl + ta * W + tb;
+                    ent[i][t] = zero ? (unsigned)ABUF : (unsigned)p * 128u + (unsigned)(((2 * hb) ^ ((p >> 1) & 7)) << 4);
+                    continue;
+                }
                 int dy = t / 3 - 1, dx = t % 3 - 1;
                 bool zero = m >= a.M;
                 if (d.pad_mode == SMIRK_PAD_REFLECT) {
@@ -251,7 +274,7 @@ __device__ __forceinline__ void conv_halo_body(const ConvArgs& a) {
             }
         }
 #pragma unroll
-        for (int t = 0; t < 9; ++t) tabA[t] = ent[0][t] | (ent[1][t] << 16);
+        for (int t = 0; t < NTAP; ++t) tabA[t] = ent[0][t] | (ent[1][t] << 16);
     }
     asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -260,8 +283,11 @@ __device__ __forceinline__ void conv_halo_body(const ConvArgs& a) {
     for (int cc = 0; cc < ncc; ++cc) {
         const int acur = A0 + (cc & 1) * ASTRIDE, anext = A0 + ((cc + 1) & 1) * ASTRIDE;
         body(cc, acur, anext, hs_ic<0>{}); body(cc, acur, anext, hs_ic<1>{}); body(cc, acur, anext, hs_ic<2>{});
-        body(cc, acur, anext, hs_ic<3>{}); body(cc, acur, anext, hs_ic<4>{}); body(cc, acur, anext, hs_ic<5>{});
-        body(cc, acur, anext, hs_ic<6>{}); body(cc, acur, anext, hs_ic<7>{}); body(cc, acur, anext, hs_ic<8>{});
+        body(cc, acur, anext, hs_ic<3>{});
+        if constexpr (!UP) {
+            body(cc, acur, anext, hs_ic<4>{}); body(cc, acur, anext, hs_ic<5>{});
+            body(cc, acur, anext, hs_ic<6>{}); body(cc, acur, anext, hs_ic<7>{}); body(cc, acur, anext, hs_ic<8>{});
+        }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 // the over-fetched pieces must have landed before LDS is reused
     // ---- epilogue operands, requested BEFORE the closing barriers so that the loads fly while the workgroup drains ------------------------------
@@ -273,9 +299,27 @@ __device__ __forceinline__ void conv_halo_body(const ConvArgs& a) {
     const int en = n0 + wn * 64 + eg * 8;
     f32x4 sc0 = {1.f, 1.f, 1.f, 1.f}, sc1 = sc0, sf0 = {0.f, 0.f, 0.f, 0.f}, sf1 = sf0;
     if (a.scale) { sc0 = *(const f32x4*)(a.scale + en); sc1 = *(const f32x4*)(a.scale + en + 4); }
-    if (a.shift) { sf0 = *(const f32x4*)(a.shift + en); sf1 = *(const f32x4*)(a.shift + en + 4); }
+    if (!UP && a.shift) { sf0 = *(const f32x4*)(a.shift + en); sf1 = *(const f32x4*)(a.shift + en + 4); }
     half8 resh[2][ITEMS], resl[2][ITEMS];
-    if (a.residual) {
+    // UP: every item's fine pixel (2y + dy, 2x + dx) and its shift row [class][row edge][column edge][N] — a class-dy row touches the border only at y = 0
+    // (dy = 0) or y = H - 1 (dy = 1), columns likewise — requested up front like the residual groups
+    size_t uo[2][ITEMS];
+    f32x4 us0[2][ITEMS], us1[2][ITEMS];
+    if constexpr (UP) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int it = 0; it < ITEMS; ++it) {
+                const int m = min(m0 + (wm * 2 + i) * 32 + it * 8 + erow, a.M - 1);
+                const int b = m / HW, rem = m - b * HW, y = rem / W, x = rem - y * W;
+                const int re = y == (dyc ? d.H - 1 : 0), ce = x == (dxc ? W - 1 : 0);
+                uo[i][it] = (((size_t)b * (2 * d.H) + (2 * y + dyc)) * (size_t)(2 * W) + (2 * x + dxc)) * d.Cout + en;
+                const float* const srow = a.shift + (size_t)((cls * 2 + re) * 2 + ce) * a.N + en;
+                us0[i][it] = *(const f32x4*)srow;
+                us1[i][it] = *(const f32x4*)(srow + 4);
+            }
+    }
+    if (!UP && a.residual) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -314,20 +358,23 @@ __device__ __forceinline__ void conv_halo_body(const ConvArgs& a) {
                 float v[8];
                 *(f32x4*)v = *(const f32x4*)(ebuf + row * HS_EPI_LD + eg * 8);
                 *(f32x4*)(v + 4) = *(const f32x4*)(ebuf + row * HS_EPI_LD + eg * 8 + 4);
-                const size_t o = (size_t)m * d.Cout + en;            // raster order: GEMM row m IS the NHWC pixel index
+                const size_t o = UP ? uo[i][it] : (size_t)m * d.Cout + en;   // raster order: GEMM row m IS the NHWC pixel index (UP: of the coarse tensor)
                 if (a.scale) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) { v[q] *= sc0[q]; v[4 + q] *= sc1[q]; }
                 }
-                if (a.shift) {
+                if constexpr (UP) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) { v[q] += us0[i][it][q]; v[4 + q] += us1[i][it][q]; }
+                } else if (a.shift) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) { v[q] += sf0[q]; v[4 + q] += sf1[q]; }
                 }
-                if (a.residual) {
+                if (!UP && a.residual) {
 #pragma unroll
                     for (int q = 0; q < 8; ++q) v[q] += join1(resh[i][it][q], resl[i][it][q]);
                 }
-                if (d.act == SMIRK_ACT_RELU) {
+                if (!UP && d.act == SMIRK_ACT_RELU) {
 #pragma unroll
                     for (int q = 0; q < 8; ++q) v[q] = fmaxf(v[q], 0.f);
                 }
@@ -360,6 +407,9 @@ template <int NPA, int EB>
 __global__ __launch_bounds__(512, 2) void conv_halo_stats_kernel(ConvArgs a) { conv_halo_body<NPA, EB, false, true>(a); }
 template <int NPA>
 __global__ __launch_bounds__(512, 2) void conv_halo_x1_stats_kernel(ConvArgs a) { conv_halo_body<NPA, 0, true, true>(a); }
+// the coarse half of a composed decoder level (UP above): grid = 4 classes x tiles, a.d describes the COARSE tensor, a.w = Weff, a.shift = the 16 shift rows
+template <int NPA>
+__global__ __launch_bounds__(512, 2) void conv_halo_up_kernel(ConvArgs a) { conv_halo_body<NPA, 0, false, false, true>(a); }
 
 // Serves: split-fp16, 3x3, stride 1, pad 1, NHWC out, both sources power-of-two multiples of 32 channels, N a multiple of 128, W <= 63, operands < 2 GiB.
 bool smirk_conv_halo_eligible(const ConvArgs& a) {
@@ -409,4 +459,195 @@ int smirk_conv_halo_launch(const ConvArgs& a, hipStream_t st, bool x1) {
     // the $SMIRK_HALO_EB switch and its instantiations left the library in round 5)
     if (x1) return npa <= 5 ? hs_launch<5, HS_DEFAULT_EB, true>(a, st, lds) : hs_launch<6, HS_DEFAULT_EB, true>(a, st, lds);
     return npa <= 5 ? hs_launch<5, HS_DEFAULT_EB, false>(a, st, lds) : hs_launch<6, HS_DEFAULT_EB, false>(a, st, lds);
+}
+
+// ---- decoder levels 3 / 4: ConvTranspose2d(2c -> c, k2 s2) composed into the first 3x3 convolution of the level ----------------------------------
+//   out = ReLU(scale * conv3x3(skip; W3[:, c:]) + shift + partial'),   partial'(2y + dy, 2x + dx) = scale * (sum over the class's 2 x 2 coarse taps of Weff . d + Beff)
+// as TWO launches: conv_halo_up_kernel writes partial' where `up` used to go, the unchanged conv_halo_kernel runs the skip half with partial' as its residual.
+// updeep_compose_kernel rebuilds, on every forward (the weight struct has no field for a cached image; in-place weight updates stay correct), per level:
+//   weff   [4 classes][c][4 taps * 2c]   ordinary split-fp16 conv rows, tap (ta, tb) = coarse offset (dy - 1 + ta, dx - 1 + tb)
+//   shift16[4 classes][row edge][column edge][c] fp32 = scale * (sum of W3 . bias over the fine taps inside the image)
+//   wskip  [c][9 * c]                    the skip half of the conv rows
+// from hi + lo / 2048 in fp64, re-split.  Block roles per level: 64 x 64 tiles of the (class, tap) GEMMs Weff = sum over the fine taps of the pair W3tap [c x c] .
+// Wup_sub [c x 2c] (16 fp64 k-steps per LDS stage, 4 x 4 outputs per thread), then one block per output channel for the shift rows, then the copy blocks.
+struct UpdeepLevelArgs {
+    const float *wup, *bup, *w3, *scale;
+    float *weff, *shift16, *wskip;
+    int c, blk0, ngemm, nshift;
+};
+struct UpdeepComposeArgs {
+    UpdeepLevelArgs lv[2];
+};
+
+__device__ __forceinline__ double hs_dec64(const _Float16* row, int k) {
+    return (double)(float)row[(k >> 3) * 16 + (k & 7)] + (double)(float)row[(k >> 3) * 16 + 8 + (k & 7)] * (1.0 / 2048.0);
+}
+
+__global__ __launch_bounds__(256) void updeep_compose_kernel(UpdeepComposeArgs args) {
+    __shared__ __attribute__((aligned(16))) double As[16][64];
+    __shared__ __attribute__((aligned(16))) double Bs[16][64];
+    __shared__ double S[9];
+    const int li = (int)blockIdx.x >= args.lv[1].blk0 ? 1 : 0;
+    const UpdeepLevelArgs& L = args.lv[li];
+    const int C = L.c, CIN = 2 * C, tid = threadIdx.x;
+    int r = (int)blockIdx.x - L.blk0;
+    const _Float16* const w3h = (const _Float16*)L.w3;
+    const _Float16* const wuh = (const _Float16*)L.wup;
+    if (r < L.ngemm) {
+        const int nci = CIN / 64, nco = C / 64;
+        const int ci0 = (r % nci) * 64, co0 = ((r / nci) % nco) * 64, ct = r / (nci * nco);
+        const int cls = ct >> 2, tap = ct & 3, dy = cls >> 1, dx = cls & 1, ca = dy - 1 + (tap >> 1), cb = dx - 1 + (tap & 1);
+        const int tx = tid & 15, ty = tid >> 4;
+        double acc[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
+        for (int fy = -1; fy <= 1; ++fy) {
+            if (((dy + fy) >> 1) != ca) continue;
+            for (int fx = -1; fx <= 1; ++fx) {
+                if (((dx + fx) >> 1) != cb) continue;
+                const int sub = ((dy + fy) & 1) * 2 + ((dx + fx) & 1), t3 = (fy + 1) * 3 + (fx + 1);
+                for (int cu0 = 0; cu0 < C; cu0 += 16) {
+                    if (tid < 128) {                                  // A stage: W3[co0 + row][t3][cu0 + 8 g ..]: one 8-channel group per thread, stored k-major
+                        const int row = tid >> 1, g = tid & 1;
+                        const _Float16* const src = w3h + ((size_t)((co0 + row) * 9 + t3) * CIN + cu0 + g * 8) * 2;
+                        const half8 hi = *(const half8*)src, lo = *(const half8*)(src + 8);
+#pragma unroll
+                        for (int q = 0; q < 8; ++q) As[g * 8 + q][row] = (double)(float)hi[q] + (double)(float)lo[q] * (1.0 / 2048.0);
+                    } else {                                          // B stage: Wup[sub][cu0 + krow][ci0 + 8 g ..]
+                        const int t2 = tid - 128, krow = t2 >> 3, g = t2 & 7;
+                        const _Float16* const src = wuh + ((size_t)(sub * C + cu0 + krow) * CIN + ci0 + g * 8) * 2;
+                        const half8 hi = *(const half8*)src, lo = *(const half8*)(src + 8);
+#pragma unroll
+                        for (int q = 0; q < 8; ++q) Bs[krow][g * 8 + q] = (double)(float)hi[q] + (double)(float)lo[q] * (1.0 / 2048.0);
+                    }
+                    __syncthreads();
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) {
+                        double av[4], bv[4];
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) { av[i] = As[k][ty * 4 + i]; bv[i] = Bs[k][tx * 4 + i]; }
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) acc[i][j] = fma(av[i], bv[j], acc[i][j]);
+                    }
+                    __syncthreads();
+                }
+            }
+        }
+        _Float16* const weh = (_Float16*)L.weff;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int co = co0 + ty * 4 + i, k = tap * CIN + ci0 + tx * 4;      // 4 channels = half of an 8-channel group: 4 hi halves, 4 lo halves
+            _Float16* const dst = weh + ((size_t)(cls * C + co) * 4 * CIN) * 2 + (k >> 3) * 16 + (k & 7);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float v = (float)acc[i][j];
+                const _Float16 hi = (_Float16)v;
+                dst[j] = hi;
+                dst[8 + j] = (_Float16)((v - (float)hi) * 2048.0f);
+            }
+        }
+        return;
+    }
+    r -= L.ngemm;
+    if (r < L.nshift) {                                                  // S[t] = W3[co][t][:c] . bias (wave w: taps w, w + 4, w + 8; fixed reduction order), then 16 rows
+        const int co = r, lane = tid & 63, wave = tid >> 6;
+        for (int t = wave; t < 9; t += 4) {
+            const _Float16* const w3row = w3h + ((size_t)(co * 9 + t) * CIN) * 2;
+            double s = 0.0;
+            for (int cu = lane; cu < C; cu += 64) s += hs_dec64(w3row, cu) * (double)L.bup[cu];
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+            if (lane == 0) S[t] = s;
+        }
+        __syncthreads();
+        if (tid < 16) {
+            const int ce = tid & 1, re = (tid >> 1) & 1, cls = tid >> 2, dy = cls >> 1, dx = cls & 1;
+            double acc = 0.0;
+            for (int fy = -1; fy <= 1; ++fy) {
+                if (re && fy == (dy ? 1 : -1)) continue;                  // this tap's fine row lies in the zero padding
+                for (int fx = -1; fx <= 1; ++fx) {
+                    if (ce && fx == (dx ? 1 : -1)) continue;
+                    acc += S[(fy + 1) * 3 + (fx + 1)];
+                }
+            }
+            L.shift16[tid * C + co] = (float)((double)L.scale[co] * acc);
+        }
+        return;
+    }
+    r -= L.nshift;
+    {                                                                    // skip half of the conv rows: 16-byte pieces
+        const int ppr = C / 4, idx = r * 256 + tid;
+        if (idx < 9 * C * ppr) {
+            const int row = idx / ppr, pc = idx - row * ppr;
+            *(f32x4*)(L.wskip + (size_t)row * C + pc * 4) = *(const f32x4*)(L.w3 + (size_t)row * CIN + C + pc * 4);
+        }
+    }
+}
+
+size_t smirk_updeep_weff_bytes(int c) { return (size_t)4 * c * 8 * c * 4; }      // 4 classes x c rows x (4 taps x 2c) split-fp16 pairs
+size_t smirk_updeep_shift_bytes(int c) { return (size_t)16 * c * 4; }
+size_t smirk_updeep_wskip_bytes(int c) { return (size_t)9 * c * c * 4; }
+
+static ConvArgs updeep_args(int B, int H, int W, int c0, int cout, int taps) {
+    ConvArgs a = {};
+    SmirkConvDesc& d = a.d;
+    d.B = B; d.H = H; d.W = W; d.C0 = c0; d.C1 = 0; d.Cout = cout; d.KH = d.KW = 3; d.stride = 1; d.pad_t = d.pad_l = 1; d.Ho = H; d.Wo = W;
+    d.pad_mode = SMIRK_PAD_ZERO; d.act = SMIRK_ACT_NONE; d.out_mode = SMIRK_OUT_NHWC;
+    a.Cin = c0; a.K = taps * c0; a.N = cout; a.M = B * H * W;
+    return a;
+}
+
+// A level with c output channels on a fine image of H x W takes the composed pair when conv_halo accepts BOTH launches with their own M: the coarse one
+// (B H/2 W/2 rows, 2c channels; its four Weff[class] are < 2 GiB each whenever the level's 9 * 2c rows are) and the skip half (B H W rows, c channels).
+// $SMIRK_IGEMM_HALO=0 therefore restores the two-launch level.
+bool smirk_updeep_eligible(int B, int H, int W, int c) {
+    if (B <= 0 || H < 4 || W < 4 || (H & 1) || (W & 1) || (long long)B * H * W > (1ll << 30)) return false;
+    if (!conv_fits32((long long)B * H * W * c)) return false;          // partial' / the output
+    return smirk_conv_halo_eligible(updeep_args(B, H / 2, W / 2, 2 * c, c, 4)) && smirk_conv_halo_eligible(updeep_args(B, H, W, c, c, 9));
+}
+
+int smirk_updeep_compose(const SmirkUpdeepLevel* lv, int nlv, hipStream_t st) {
+    if (nlv < 1 || nlv > 2) return SMIRK_ERR_BAD_ARG;
+    UpdeepComposeArgs args = {};
+    int blk = 0;
+    double mac = 0.0, bytes = 0.0;
+    for (int i = 0; i < 2; ++i) {
+        UpdeepLevelArgs& L = args.lv[i];
+        L.blk0 = blk;
+        if (i >= nlv) continue;                                           // (an absent level owns no block: blk0 = the grid size)
+        const SmirkUpdeepLevel& s = lv[i];
+        const int c = s.c;
+        if (c < 64 || c % 64 || !s.up || !s.conv || !s.up->w || !s.up->shift || s.up->scale || !s.conv->w || !s.conv->scale || !s.weff || !s.shift16 || !s.wskip)
+            return SMIRK_ERR_BAD_ARG;
+        L.wup = (const float*)s.up->w; L.bup = s.up->shift; L.w3 = (const float*)s.conv->w; L.scale = s.conv->scale;
+        L.weff = (float*)s.weff; L.shift16 = (float*)s.shift16; L.wskip = (float*)s.wskip;
+        L.c = c; L.ngemm = 16 * (c / 64) * (2 * c / 64); L.nshift = c;
+        blk += L.ngemm + L.nshift + (9 * c * (c / 4) + 255) / 256;
+        mac += 4.0 * 9 * c * c * 2 * c;
+        bytes += 4.0 * (4.0 * c * 2 * c + 18.0 * c * c + 32.0 * c * c + 9.0 * c * c);
+    }
+    if (g_smirk_prof_on) smirk_prof_next("updeep_compose_kernel", 2.0 * mac, bytes);
+    SMIRK_LAUNCH(updeep_compose_kernel, dim3(blk), dim3(256), 0, st, args);
+    return smirk_launch_status();
+}
+
+// launch 1: partial'[B][H][W][c] from the coarse tensor d[B][H/2][W/2][2c]
+int smirk_updeep_coarse_launch(const SmirkUpdeepLevel* lv, const void* d, void* partial, int B, int H, int W, hipStream_t st) {
+    if (!lv || !d || !partial || !smirk_updeep_eligible(B, H, W, lv->c)) return SMIRK_ERR_UNSUPPORTED;
+    ConvArgs a = updeep_args(B, H / 2, W / 2, 2 * lv->c, lv->c, 4);
+    a.in0 = (const float*)d; a.w = (const float*)lv->weff; a.scale = lv->conv->scale; a.shift = (const float*)lv->shift16; a.out = (float*)partial;
+    constexpr size_t lds = 4 * HS_BN * 128 + 2 * (5 * 8 * 1024 + 128);        // four ring stages + two 5-piece halo buffers (256 + W + 1 <= 320 rows for W <= 63)
+    if (const int rc = smirk_raise_dynamic_lds((const void*)conv_halo_up_kernel<5>, 160 * 1024)) return rc;
+    const int ntm = (a.M + HS_BM - 1) / HS_BM, ntn = a.N / HS_BN;
+    if (g_smirk_prof_on) {
+        const double px = (double)a.M;
+        smirk_prof_next("conv_halo_up_kernel<5>[256x128,8w,halo,composed upconv]", 2.0 * (4.0 * a.M) * a.N * a.K,
+                        4.0 * (px * a.Cin + 4.0 * px * a.N + 4.0 * a.N * a.K));
+    }
+    SMIRK_LAUNCH((conv_halo_up_kernel<5>), dim3(4 * ntm * ntn), dim3(512), lds, st, a);
+    return smirk_launch_status();
 }

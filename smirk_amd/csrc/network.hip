@@ -52,6 +52,9 @@ struct GenPlan {
     Rot rot;
     void* upcat_w[2];   // decoder levels 1 / 2 (index = l): composed ConvTranspose x conv weights and shift rows (conv_upcat.hip), rebuilt by every forward
     void* upcat_s[2];
+    void* updeep_w[2];  // decoder levels 3 / 4 (index = l - 2): composed coarse-tap weights, shift rows and skip-half conv rows (conv_halo.hip), rebuilt by every forward
+    void* updeep_s[2];
+    void* updeep_k[2];
     size_t total;
 };
 
@@ -67,6 +70,12 @@ GenPlan plan_generator(const SmirkGeneratorWeights* w, int B, int H, int W, void
         const bool on = w->precision == SMIRK_PRECISION_F16X3 && f == 32;
         p.upcat_w[l] = on ? a.take(smirk_conv3x3_upcat_weff_bytes(f << l)) : nullptr;
         p.upcat_s[l] = on ? a.take(smirk_conv3x3_upcat_shift_bytes(f << l)) : nullptr;
+    }
+    for (int l = 2; l < 4; ++l) {
+        const bool on = w->precision == SMIRK_PRECISION_F16X3 && f == 32;
+        p.updeep_w[l - 2] = on ? a.take(smirk_updeep_weff_bytes(f << l)) : nullptr;
+        p.updeep_s[l - 2] = on ? a.take(smirk_updeep_shift_bytes(f << l)) : nullptr;
+        p.updeep_k[l - 2] = on ? a.take(smirk_updeep_wskip_bytes(f << l)) : nullptr;
     }
     p.total = smirk_align_up(a.off, 256);
     return p;
@@ -135,6 +144,28 @@ static int generator_forward_body(const SmirkGeneratorWeights* w, const float* a
         if (Ca != 3 || Cb != 3 || w->cin_pad != 8) return SMIRK_ERR_UNSUPPORTED;
         TRY(smirk_pack_generator_input(a, b, (float*)p.x, B, H, W, stream));
     }
+    // ---- decoder levels 3 / 4 (l = 2, 3): the ConvTranspose composed into the level's first convolution as two launches (conv_halo.hip) where
+    // conv_halo takes both; their weights are composed by ONE launch here, on the caller's stream ahead of the fork event, so that every sub-batch chain reads them.
+    // A chain decides again with its own frame count (ud_on says whether the weights exist).  $SMIRK_IGEMM_HALO=0 restores the two-launch levels.
+    SmirkUpdeepLevel ud[2];
+    bool ud_on[2] = {false, false};
+    {
+        SmirkUpdeepLevel todo[2];
+        int n = 0;
+        for (int l = 2; l < 4; ++l) {
+            ud[l - 2] = SmirkUpdeepLevel{f << l, &w->up[3 - l], &w->dec[3 - l][0], p.updeep_w[l - 2], p.updeep_s[l - 2], p.updeep_k[l - 2]};
+            ud_on[l - 2] = split && f == 32 && smirk_updeep_eligible(B, H >> l, W >> l, f << l);
+            if (ud_on[l - 2]) todo[n++] = ud[l - 2];
+        }
+        if (n) TRY(smirk_updeep_compose(todo, n, (hipStream_t)stream));
+    }
+    // launch 1 writes partial' where `up` used to go; launch 2 is the ordinary 3x3 convolution over the skip tensor with partial' as its residual
+    auto updeep = [&](int l, int nb, int h, int wd, const void* coarse, const void* skip, void* partial, void* out, void* strm) -> int {
+        const SmirkUpdeepLevel& u = ud[l - 2];
+        TRY(smirk_updeep_coarse_launch(&u, coarse, partial, nb, h, wd, (hipStream_t)strm));
+        const SmirkConvLayer half{u.wskip, u.conv->scale, u.conv->shift};
+        return conv_call(true, desc3x3(nb, h, wd, u.c, 0, u.c, false, true), skip, nullptr, half, partial, out, strm);
+    };
     auto pool = [&](const void* in, void* out, int h, int wd, int c) {
         return split ? smirk_maxpool2x2_split16(in, out, B, h, wd, c, stream) : smirk_maxpool2x2_nhwc((const float*)in, (float*)out, B, h, wd, c, stream);
     };
@@ -291,10 +322,14 @@ static int generator_forward_body(const SmirkGeneratorWeights* w, const float* a
         const void* dc = cur16;
         for (int l = 3; l >= L0; --l) {                             // decoder levels of the section: ConvTranspose2d, two-source conv with the skip, conv
             const int h = H >> l, wd = W >> l, c = f << l;
-            void* up = p.rot.pick(dc, nullptr);
-            TRY(conv_call(split, desc1x1(nb, h / 2, wd / 2, 2 * c, c, false, true), P(dc), nullptr, w->up[3 - l], nullptr, Pw(up), strm));
+            void* up = p.rot.pick(dc, nullptr);                     // (composed level: partial')
             void* d1 = p.rot.pick(up, nullptr);
-            TRY(conv_call(split, desc3x3(nb, h, wd, c, c, c, false, true), P(up), N(p.e[l], h, wd, c), w->dec[3 - l][0], nullptr, Pw(d1), strm));
+            if (ud_on[l - 2] && smirk_updeep_eligible(nb, h, wd, c)) {
+                TRY(updeep(l, nb, h, wd, P(dc), N(p.e[l], h, wd, c), Pw(up), Pw(d1), strm));
+            } else {
+                TRY(conv_call(split, desc1x1(nb, h / 2, wd / 2, 2 * c, c, false, true), P(dc), nullptr, w->up[3 - l], nullptr, Pw(up), strm));
+                TRY(conv_call(split, desc3x3(nb, h, wd, c, c, c, false, true), P(up), N(p.e[l], h, wd, c), w->dec[3 - l][0], nullptr, Pw(d1), strm));
+            }
             const bool last = l == L0;
             void* d2 = last ? p.rot.pick(d1, in) : p.rot.pick(d1, nullptr);
             TRY(conv_call(split, desc3x3(nb, h, wd, c, 0, c, false, true), P(d1), nullptr, w->dec[3 - l][1], nullptr, last ? Nw(d2, h, wd, c) : Pw(d2), strm));
@@ -338,6 +373,11 @@ static int generator_forward_body(const SmirkGeneratorWeights* w, const float* a
             // levels 1 / 2: the ConvTranspose composed into the convolution that reads it (conv_upcat.hip) — no `up` tensor; $SMIRK_CONV_RING=0 restores the two launches
             t1 = p.rot.pick(dcur, nullptr);
             TRY(smirk_conv3x3_upcat_launch(c, dcur, p.e[l], &w->up[3 - l], &w->dec[3 - l][0], t1, B, h, wd, p.upcat_w[l], p.upcat_s[l], (hipStream_t)stream));
+        } else if (l >= 2 && ud_on[l - 2]) {
+            // level 3: the ConvTranspose composed into the convolution as two launches (above) — no `up` tensor; $SMIRK_IGEMM_HALO=0 restores the old pair
+            void* pp = p.rot.pick(dcur, nullptr);
+            t1 = p.rot.pick(pp, nullptr);
+            TRY(updeep(l, B, h, wd, dcur, p.e[l], pp, t1, stream));
         } else {
             void* up = p.rot.pick(dcur, nullptr);
             TRY(conv_call(split, desc1x1(B, h / 2, wd / 2, 2 * c, c, false, true), dcur, nullptr, w->up[3 - l], nullptr, up, stream));

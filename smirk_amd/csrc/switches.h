@@ -4,7 +4,10 @@
 //
 // variable                          values: what smirk_switch() returns, what it selects                                  default         used by
 // SMIRK_IGEMM_HALO                  "0": 0, deep 3x3 convolutions stay off conv_halo_kernel; anything else ("a..."          1               tests/test_conv_gpu.py
-//                                   included): 1, every eligible geometry on conv_halo_kernel
+//                                   included): 1, every eligible geometry on conv_halo_kernel.  "0" also puts the      tests/test_updeep_gpu.py
+//                                   generator's decoder levels 3 / 4 back on their two launches (ConvTranspose, then
+//                                   the convolution over cat(up, skip)) instead of conv_halo_up_kernel + the skip-half
+//                                   convolution (their eligibility is conv_halo's)
 // SMIRK_IGEMM_PP                    "0": 0, conv_pp_kernel off; "a...": 2, conv_pp_kernel for every eligible shape         1 (<= 16x16     tests/test_conv_gpu.py
 //                                   (not only images of at most 256 pixels); anything else: 1                             images)
 // SMIRK_CONV_RING                   "0": 0, the 64-output-channel ring kernels off (round-3 kernels) and the generator's   1               tests/test_conv_gpu.py,
