@@ -282,6 +282,27 @@ HANDOFF_SIGS = {
 }
 HANDOFF_EXPORTS = tuple(HANDOFF_SIGS)
 
+# The extension table of include/smirk_generator_plan.h (what a whole-network generator entry would launch, answered by generator_plan without touching device
+# memory; for tests and tools, nothing on the hot path calls it): the same shared object, a version of its own.
+GENPLAN_ABI_VERSION = 1
+GEN_MAX_CHAINS = 3                                                     # include/smirk_generator_plan.h SMIRK_GEN_MAX_CHAINS
+GEN_INPUTS = ("PACKED", "SPLIT_PACK", "NHWC_PAD", "PACK_F32")          # enum SmirkGenInput, by code
+GEN_ENCODER_FAMILIES = ("ENC1_FUSED", "CONV_POOLFUSED", "CONV_CONV_POOL")   # enum SmirkGenEncoder, by code
+GEN_DECODER_FAMILIES = ("UPCAT", "UPDEEP", "PAIR")                     # enum SmirkGenDecoder, by code
+
+
+class SmirkGeneratorPlanReport(C.Structure):
+    _fields_ = [("input", C.c_int32), ("nchain", C.c_int32), ("chain_b0", C.c_int32 * GEN_MAX_CHAINS), ("chain_nb", C.c_int32 * GEN_MAX_CHAINS),
+                ("section_from", C.c_int32), ("enc", C.c_int32 * 4), ("dec", C.c_int32 * GEN_MAX_CHAINS * 4), ("compose_mask", C.c_int32),
+                ("fused_tail", C.c_int32), ("workspace_bytes", C.c_uint64)]
+
+
+GENPLAN_SIGS = {
+    "smirk_genplan_abi_version": (_i, []),
+    "smirk_generator_plan": (_i, [C.POINTER(SmirkGeneratorWeights), _i, _i, _i, _i, _i, _i, C.POINTER(SmirkGeneratorPlanReport)]),
+}
+GENPLAN_EXPORTS = tuple(GENPLAN_SIGS)
+
 _LIB = None
 
 
@@ -297,12 +318,13 @@ def lib():
             raise SmirkHipError(f"{LIB_PATH} not found: build it with `python -m smirk_amd.build` "
                                 "(smirk_amd has no CPU / eager fallback)")
         L = C.CDLL(LIB_PATH)
-        for table in (_SIGS, MICA_SIGS, EMOTION_SIGS, OPTIM_SIGS, HANDOFF_SIGS):
+        for table in (_SIGS, MICA_SIGS, EMOTION_SIGS, OPTIM_SIGS, HANDOFF_SIGS, GENPLAN_SIGS):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)       # AttributeError => header / library mismatch
                 fn.restype, fn.argtypes = res, args
         if L.smirk_abi_version() != ABI_VERSION or L.smirk_mica_abi_version() != MICA_ABI_VERSION or L.smirk_emotion_abi_version() != EMOTION_ABI_VERSION or \
-                L.smirk_optim_abi_version() != OPTIM_ABI_VERSION or L.smirk_handoff_abi_version() != HANDOFF_ABI_VERSION:
+                L.smirk_optim_abi_version() != OPTIM_ABI_VERSION or L.smirk_handoff_abi_version() != HANDOFF_ABI_VERSION or \
+                L.smirk_genplan_abi_version() != GENPLAN_ABI_VERSION:
             raise SmirkHipError("libsmirk_hip.so ABI version mismatch; rebuild")
         _LIB = L
     return _LIB

@@ -782,18 +782,28 @@ extern "C" int smirk_conv_igemm_f32(const SmirkConvDesc* d, const float* in0, co
 // Network tail in one launch: conv3x3 (split16 in) + BN + ReLU + 1x1 conv (Cout 32 -> fcout <= 4) + bias + sigmoid -> NCHW fp32.
 // conv3x3 + BN + ReLU with the 2 x 2 max-pool of its output produced by the same launch (the U-Net's encoder blocks: `enc = block(x); pool(enc)`,
 // smirk_generator.py:52-59).  SMIRK_ERR_UNSUPPORTED when no kernel with a fused pool serves the shape (the caller then runs conv and pool separately).
+// What the two fused entries below serve, for whoever plans a schedule (plan_generator, network.hip) and for the entries themselves: a shape the ring kernel
+// (fused pool) or the patch kernel (fused tail) takes.  Neither looks at a pointer.
+bool smirk_conv3x3_pool_supported(const SmirkConvDesc* d) {
+    if (!d || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->C0 <= 0 || d->C1 < 0) return false;
+    const int bc = conv_batch_chunk(d, true);                      // batch chunks below 2 GiB each: eligibility is a property of the chunk
+    if (bc <= 0) return false;
+    SmirkConvDesc d0 = *d;
+    d0.B = d->B < bc ? d->B : bc;
+    return d0.Cout == 64 && smirk_conv3x3_ring64_eligible(&d0, false);
+}
+
+bool smirk_conv3x3_tail_supported(const SmirkConvDesc* d, int fcout) {
+    return d && fcout > 0 && fcout <= 4 && d->Cout == 32 && d->act == SMIRK_ACT_RELU && smirk_conv3x3_patch_eligible(d, false);
+}
+
 extern "C" int smirk_conv3x3_pool_f16x3(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale, const float* shift, void* out,
                                         void* pooled, void* stream) {
     if (!d || !in0 || !w || !out || !pooled) return SMIRK_ERR_BAD_ARG;
     if (d->C0 % 8 || d->C1 % 8 || (d->C1 > 0 && !in1) || d->H % 2 || d->W % 2) return SMIRK_ERR_BAD_ARG;
     if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->C0 <= 0) return SMIRK_ERR_BAD_ARG;
-    const int bc = conv_batch_chunk(d, true);                      // batch chunks below 2 GiB each: eligibility is a property of the chunk
-    if (bc <= 0) return SMIRK_ERR_UNSUPPORTED;
-    {
-        SmirkConvDesc d0 = *d;
-        d0.B = d->B < bc ? d->B : bc;
-        if (d0.Cout != 64 || !smirk_conv3x3_ring64_eligible(&d0, false)) return SMIRK_ERR_UNSUPPORTED;
-    }
+    if (!smirk_conv3x3_pool_supported(d)) return SMIRK_ERR_UNSUPPORTED;
+    const int bc = conv_batch_chunk(d, true);
     return conv_for_batch_chunks(d, bc, [&](const ConvChunk& c) {       // (same-size output, H and W even: the pooled tensor is a quarter of it)
         return smirk_conv3x3_ring64_launch(&c.d, (const float*)in0 + c.in0, chunk_ptr(in1, c.in1), w, scale, shift, (float*)out + c.out, (float*)pooled + c.out / 4,
                                            (hipStream_t)stream);
@@ -805,7 +815,7 @@ extern "C" int smirk_conv3x3_tail_f16x3(const SmirkConvDesc* d, const void* in0,
                                         void* stream) {
     if (!d || !in0 || !w || !fw || !out_nchw || fcout <= 0 || fcout > 4 || d->Cout != 32) return SMIRK_ERR_BAD_ARG;
     if (d->C0 % 8 || d->C1 % 8 || (d->C1 > 0 && !in1) || d->act != SMIRK_ACT_RELU) return SMIRK_ERR_BAD_ARG;
-    if (!smirk_conv3x3_patch_eligible(d, false)) return SMIRK_ERR_UNSUPPORTED;
+    if (!smirk_conv3x3_tail_supported(d, fcout)) return SMIRK_ERR_UNSUPPORTED;
     const int bc = (d->B > 0 && d->H > 0 && d->W > 0 && d->C0 > 0 && d->C1 >= 0) ? conv_batch_chunk(d, true) : d->B;
     if (bc >= d->B) return smirk_conv3x3_patch_launch(d, in0, in1, w, scale, shift, nullptr, (hipStream_t)stream, fw, fb, out_nchw, fcout);
     return conv_for_batch_chunks(d, bc, [&](const ConvChunk& c) {       // (the NCHW output has its own stride per image)

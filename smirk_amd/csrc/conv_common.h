@@ -139,6 +139,10 @@ bool smirk_conv3x3_patch_eligible(const SmirkConvDesc* d, bool has_residual);
 int smirk_conv3x3_patch_launch(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale,
                                const float* shift, void* out, hipStream_t st, const float* fw, const float* fb, float* fout,
                                int fcout);
+// conv.hip: what smirk_conv3x3_pool_f16x3 (conv + BN + ReLU + 2 x 2 max-pool on the ring kernel) and smirk_conv3x3_tail_f16x3 (conv + BN + ReLU + 1x1 conv + sigmoid on
+// the patch kernel) serve; each entry answers SMIRK_ERR_UNSUPPORTED exactly where its predicate says no
+bool smirk_conv3x3_pool_supported(const SmirkConvDesc* d);
+bool smirk_conv3x3_tail_supported(const SmirkConvDesc* d, int fcout);
 // conv_halo.hip: the ping-pong schedule with the A operand staged once per channel chunk (one pixel halo serves all nine taps); 256-row tiles x 4 wave rows
 #define HS_BM 256
 #define HS_WGM 4

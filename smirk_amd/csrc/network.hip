@@ -4,12 +4,15 @@
 //   smirk_backbone_forward    one sub-encoder of SmirkEncoder.forward: timm MobileNetV3-minimal features[-1] -> GAP -> Linear (+ clamps)
 //                             (src/smirk_encoder.py:34-45, :66-73, :95-110; backbone per SURVEY.md App. A)
 //
-// These are pure schedules over the per-layer entries of conv.hip / conv_patch.hip / encoder_ops.hip / encoder_head.hip / mbconv.hip / mbconv_image.hip /
-// mbconv_s2.hip: which kernel serves a convolution is still decided by those dispatchers.  Which ENTRY serves a backbone block is decided here, once, by
-// backbone_plan (one priority table, backbone_block_family); smirk_backbone_forward is a switch over that plan, smirk_backbone_workspace_bytes returns its bytes and
-// smirk_backbone_plan reports its families without touching the device.  What moves here is the host-side walk (~60 launches for the generator, ~35-50 per
-// backbone): from Python + ctypes (~15 ms per 128-frame step, more than the GPU time of the step) to straight C++ (a few hundred
-// microseconds), and the activation memory from the framework's allocator to a caller-provided workspace that is laid out once:
+// Both halves of this file have the same frame.  Which kernel serves a convolution is decided by the dispatchers of conv.hip / conv_patch.hip / encoder_ops.hip /
+// encoder_head.hip / mbconv*.hip; which ENTRY serves a level of the generator or a block of a backbone is decided here, once per call, by a pure plan function:
+//                  plan                                        forward: a walk over the plan      bytes of the plan                   the plan, device-free
+//   generator      plan_generator (+ gen_chain_count)          smirk_generator_forward[_packed]   smirk_generator_workspace_bytes     smirk_generator_plan
+//   backbone       backbone_plan (backbone_block_family)       smirk_backbone_forward             smirk_backbone_workspace_bytes      smirk_backbone_plan
+// A plan reads the weights' shape fields, the call's sizes and the kernels' own `*_supported` / `*_eligible` statements; it follows no pointer.  The forwards launch
+// what the plan says and return what a launch returns.  What moves here is the host-side walk (~60 launches for the generator, ~35-50 per backbone): from Python +
+// ctypes (~15 ms per 128-frame step, more than the GPU time of the step) to straight C++ (a few hundred microseconds), and the activation memory from the
+// framework's allocator to a caller-provided workspace that is laid out once:
 //   * U-Net skip tensors e1..e4 have fixed slots,
 //   * everything else rotates through three scratch slots sized for the largest temporary (a layer reads at most two temporaries —
 //     input and residual — and writes one).
@@ -20,6 +23,7 @@
 
 #include "conv_common.h"
 #include "../../include/smirk_handoff.h"
+#include "../../include/smirk_generator_plan.h"
 
 namespace {
 
@@ -45,41 +49,6 @@ struct Rot {
 };
 
 inline size_t act_bytes(int B, int H, int W, int C) { return (size_t)B * H * W * C * 4; }
-
-struct GenPlan {
-    void* x;         // packed network input [B][H][W][cin_pad]
-    void* e[4];      // skip tensors
-    Rot rot;
-    void* upcat_w[2];   // decoder levels 1 / 2 (index = l): composed ConvTranspose x conv weights and shift rows (conv_upcat.hip), rebuilt by every forward
-    void* upcat_s[2];
-    void* updeep_w[2];  // decoder levels 3 / 4 (index = l - 2): composed coarse-tap weights, shift rows and skip-half conv rows (conv_halo.hip), rebuilt by every forward
-    void* updeep_s[2];
-    void* updeep_k[2];
-    size_t total;
-};
-
-GenPlan plan_generator(const SmirkGeneratorWeights* w, int B, int H, int W, void* ws) {
-    Arena a{(char*)ws, 0};
-    GenPlan p;
-    const int f = w->features;
-    p.x = a.take(act_bytes(B, H, W, w->cin_pad));
-    for (int l = 0; l < 4; ++l) p.e[l] = a.take(act_bytes(B, H >> l, W >> l, f << l));
-    const size_t big = act_bytes(B, H, W, f);                       // the largest temporary: enc1conv1 out, up1, dec1conv1 out
-    for (int i = 0; i < 3; ++i) p.rot.slot[i] = a.take(big);
-    for (int l = 0; l < 2; ++l) {
-        const bool on = w->precision == SMIRK_PRECISION_F16X3 && f == 32;
-        p.upcat_w[l] = on ? a.take(smirk_conv3x3_upcat_weff_bytes(f << l)) : nullptr;
-        p.upcat_s[l] = on ? a.take(smirk_conv3x3_upcat_shift_bytes(f << l)) : nullptr;
-    }
-    for (int l = 2; l < 4; ++l) {
-        const bool on = w->precision == SMIRK_PRECISION_F16X3 && f == 32;
-        p.updeep_w[l - 2] = on ? a.take(smirk_updeep_weff_bytes(f << l)) : nullptr;
-        p.updeep_s[l - 2] = on ? a.take(smirk_updeep_shift_bytes(f << l)) : nullptr;
-        p.updeep_k[l - 2] = on ? a.take(smirk_updeep_wskip_bytes(f << l)) : nullptr;
-    }
-    p.total = smirk_align_up(a.off, 256);
-    return p;
-}
 
 int conv_call(bool split, const SmirkConvDesc& d, const void* in0, const void* in1, const SmirkConvLayer& L, const void* residual, void* out,
               void* stream) {
@@ -117,283 +86,360 @@ bool gen_args_ok(const SmirkGeneratorWeights* w, int B, int H, int W) {
     return w->precision == SMIRK_PRECISION_F32 && w->features % 8 == 0 && w->cin_pad % 4 == 0 && w->cin_pad >= w->in_channels;
 }
 
+// ---- how many sub-batch chains run the deep part of the network ---------------------------------------------------------------------------------------------------
+// The layers at H/4 and below rarely fill whole rounds of workgroups on the 256 CUs (14 x 14 x 512: 196 B / 256 tiles x 4 = 1.53 rounds at 128 frames = 2 rounds
+// of time, 3.06 -> 4 at 256; the 28 x 28 and 56 x 56 layers likewise), and each waits for the one before it.  Frames are independent, so the SECTION — encoder4,
+// bottleneck, ResNet blocks, decoder4 (levels l >= GEN_SECTION_FROM) — runs as TWO (optionally three) sub-batch chains on as many streams (the caller's and
+// library-owned side streams, forked / joined with events): while one chain's layer drains its partial last round the other chain's workgroups take the free CUs.
+// Bit-identical results (batch invariance, tests/test_scale_gpu.py run with it forced).  Measured with the RCCL gather enqueued, same box (profiles/r04l_, r04m_,
+// r04n_): +3.2 % at 128 frames per pass, +4.5 % at 256, +1.2 % at 1024 for the H/8 + H/16 part -> taken when > 5 % of a 14 x 14 layer's last round would idle.
+// $SMIRK_GEN_SPLIT_CHAINS=0 / 2 / 3 selects the number of chains (the A/B switch of tests/test_generator_gpu.py).  The section starts at H/8: starting it at H/4
+// measured 8,801 vs 8,857 faces/s at 128 frames, 9,406 vs 9,473 at 256, 9,872 vs 9,782 at 1024 (profiles/r04n_chain_from.txt; the 56 x 56 layers fill their rounds) and
+// the switch for it left the library.  Batches below 16 frames are never split by the heuristic (a fork / join costs more than the idle part of their only round).
+constexpr int GEN_SECTION_FROM = 3;
+
+// The WISH, a pure function: taps copy whole tensors and the launch profiler times launches on ONE stream, so either keeps one chain; `forced` is the switch's value.
+int gen_chain_count(int features, int B, int H, int W, bool taps, bool profiling, int forced, int cus) {
+    if (B < 2 || taps || profiling) return 1;
+    const double rounds = ((double)B * (H >> 4) * (W >> 4) / 256.0) * ((features << 4) / 128.0) / cus;      // 256 x 128 tiles of a 14 x 14 layer per CU
+    const double full = (double)(long long)(rounds + 0.999999);
+    int n = B >= 16 && full > 0 && (full - rounds) / full > 0.05 ? 2 : 1;
+    if (forced) n = forced;
+    return n > B ? B : n;
+}
+
+int gen_chain_wish(const SmirkGeneratorWeights* w, int B, int H, int W, bool taps) {
+    return gen_chain_count(w->features, B, H, W, taps, g_smirk_prof_on, smirk_switch(SMIRK_SW_GEN_SPLIT_CHAINS), smirk_device_cus());
+}
+
+// The GRANT.  Side streams and the fork / join events are owned per HOST THREAD and device (thread_local): two threads driving the same device neither race on the
+// lazy creation nor record / wait on each other's events; created once, reused by every forward of that thread (re-recording an event only affects later waits).
+// RAII: a host thread that ends releases its side streams and events (a thread pool of short-lived workers leaked 2 streams + 3 events per thread; advisor r05).
+// The destructor runs at thread exit; work still queued on a side stream completes first (hipStreamDestroy defers the release until the stream drains).
+struct ChainResources {
+    hipStream_t side[64][2] = {};
+    hipEvent_t ev[64][3] = {};
+    ~ChainResources() {
+        // the MAIN thread's thread_locals are destroyed inside exit(), where the HIP runtime may already be shutting down: the process exit reclaims them
+        if ((long)syscall(SYS_gettid) == (long)getpid()) return;
+        int cur = 0;
+        const bool have = hipGetDevice(&cur) == hipSuccess;
+        for (int d = 0; d < 64; ++d) {
+            bool any = false;
+            for (int k = 0; k < 2; ++k) any = any || side[d][k];
+            for (int k = 0; k < 3; ++k) any = any || ev[d][k];
+            if (!any) continue;
+            if (hipSetDevice(d) != hipSuccess) { (void)hipGetLastError(); continue; }
+            for (int k = 0; k < 2; ++k) if (side[d][k]) (void)hipStreamDestroy(side[d][k]);
+            for (int k = 0; k < 3; ++k) if (ev[d][k]) (void)hipEventDestroy(ev[d][k]);
+        }
+        if (have) (void)hipSetDevice(cur);
+        (void)hipGetLastError();
+    }
+};
+
+struct ChainGrant {
+    int n;                                                          // `want`, or 1: no fork
+    hipStream_t side[2];
+    hipEvent_t fork, join[2];
+};
+
+// `want` chains with their streams and events, or ONE chain: while `stream` is being captured (or cannot say), without a current device, or when an event or a
+// stream cannot be created.
+ChainGrant grant_chains(int want, hipStream_t stream) {
+    ChainGrant g = {1, {nullptr, nullptr}, nullptr, {nullptr, nullptr}};
+    if (want < 2) return g;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return g; }
+    thread_local ChainResources res;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return g; }
+    for (int k = 0; k < 3; ++k)
+        if (!res.ev[dev][k] && hipEventCreateWithFlags(&res.ev[dev][k], hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); res.ev[dev][k] = nullptr; return g; }
+    for (int k = 0; k + 1 < want; ++k) {
+        if (!res.side[dev][k] && hipStreamCreateWithFlags(&res.side[dev][k], hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); res.side[dev][k] = nullptr; return g; }
+        g.side[k] = res.side[dev][k];
+    }
+    g.fork = res.ev[dev][0]; g.join[0] = res.ev[dev][1]; g.join[1] = res.ev[dev][2];
+    g.n = want;
+    return g;
+}
+
+// ---- the plan -----------------------------------------------------------------------------------------------------------------------------------------------------
+// Everything a generator forward decides before it launches (DESIGN.md 28 has the family table): a pure function of the weights' SHAPE fields, the sources' channel
+// counts (0 + 0: the packed entry), the batch, the image size, whether taps are wanted and the chain count it is granted.  It follows no pointer (`ws` only becomes
+// addresses); the kernel switches reach it through the kernels' own `*_supported` / `*_eligible` statements, which are not restated here.  `r` is what
+// smirk_generator_plan reports (include/smirk_generator_plan.h describes every field); r.input = -1 stands for the fp32 pair of sources that no pack kernel serves.
+// Levels l = 0..3 work at H >> l x W >> l with features << l channels (encoder l + 1, decoder l + 1).
+struct GenPlan {
+    SmirkGeneratorPlanReport r;
+    bool fast;                                                      // split-fp16 with 32 features: what every specialised generator kernel is written for
+    void *x, *e[4];                                                 // packed network input [B][H][W][cin_pad], skip tensors
+    Rot rot;
+    void *upcat_w[2], *upcat_s[2];                                  // levels 0 / 1 (index = l): composed weights and shift rows (conv_upcat.hip), rebuilt by every forward
+    void *updeep_w[2], *updeep_s[2], *updeep_k[2];                  // levels 2 / 3 (index = l - 2): composed coarse-tap weights, shift rows, skip-half conv rows (conv_halo.hip)
+};
+
+GenPlan plan_generator(const SmirkGeneratorWeights* w, int Ca, int Cb, int B, int H, int W, bool taps, int nchain, void* ws) {
+    GenPlan p = {};
+    SmirkGeneratorPlanReport& r = p.r;
+    const bool split = w->precision == SMIRK_PRECISION_F16X3;
+    const int f = w->features;
+    p.fast = split && f == 32;
+    r.input = Ca == 0 && Cb == 0 ? SMIRK_GEN_INPUT_PACKED : split ? SMIRK_GEN_INPUT_SPLIT_PACK : Cb == 0 ? SMIRK_GEN_INPUT_NHWC_PAD
+              : Ca == 3 && Cb == 3 && w->cin_pad == 8 ? SMIRK_GEN_INPUT_PACK_F32 : -1;
+    r.nchain = nchain;
+    r.section_from = GEN_SECTION_FROM;
+    for (int k = 0; k < nchain; ++k) {                              // chain k owns frames [B k / n, B (k + 1) / n)
+        r.chain_b0[k] = (int)((long long)B * k / nchain);
+        r.chain_nb[k] = (int)((long long)B * (k + 1) / nchain) - r.chain_b0[k];
+    }
+    for (int l = 0; l < 4; ++l) {
+        const int h = H >> l, wd = W >> l, c = f << l;
+        const bool whole = l < GEN_SECTION_FROM;                    // above the section: one launch sequence for the whole batch
+        const SmirkConvDesc conv2 = desc3x3(B, h, wd, c, 0, c, false, true);
+        r.enc[l] = l == 0 && split && smirk_enc1_fused_supported(w->cin_pad, f, h, wd) ? SMIRK_GEN_ENC_ENC1_FUSED
+                   : whole && split && smirk_conv3x3_pool_supported(&conv2) ? SMIRK_GEN_ENC_CONV_POOLFUSED : SMIRK_GEN_ENC_CONV_CONV_POOL;
+        // Levels 0 / 1 compose their weights inside their own entry.  Levels 2 / 3: the composed weights exist only where the WHOLE batch is eligible (ONE launch builds
+        // them ahead of the fork, for every chain to read); a chain takes UPDEEP where they exist and its own frames are eligible, so a batch whose level tensor passes
+        // 2 GiB runs PAIR in every chain.
+        const bool composed = l >= 2 && p.fast && smirk_updeep_eligible(B, h, wd, c);
+        if (composed) r.compose_mask |= 1 << l;
+        for (int k = 0; k < SMIRK_GEN_MAX_CHAINS; ++k) {
+            if (k >= (whole ? 1 : nchain)) r.dec[l][k] = -1;
+            else if (l < 2) r.dec[l][k] = p.fast && smirk_conv3x3_upcat_eligible(c, h, wd) ? SMIRK_GEN_DEC_UPCAT : SMIRK_GEN_DEC_PAIR;
+            else r.dec[l][k] = composed && smirk_updeep_eligible(whole ? B : r.chain_nb[k], h, wd, c) ? SMIRK_GEN_DEC_UPDEEP : SMIRK_GEN_DEC_PAIR;
+        }
+    }
+    const SmirkConvDesc last = desc3x3(B, H, W, f, 0, f, false, true);
+    r.fused_tail = p.fast && !taps && H >= 64 && smirk_conv3x3_tail_supported(&last, w->out_channels);
+    // Workspace: the layout depends on neither switches, taps nor chains (callers size and cache workspaces from smirk_generator_workspace_bytes).
+    Arena a{(char*)ws, 0};
+    p.x = a.take(act_bytes(B, H, W, w->cin_pad));
+    for (int l = 0; l < 4; ++l) p.e[l] = a.take(act_bytes(B, H >> l, W >> l, f << l));
+    for (int i = 0; i < 3; ++i) p.rot.slot[i] = a.take(act_bytes(B, H, W, f));      // the largest temporary: enc1conv1 out, up1, dec1conv1 out
+    for (int l = 0; l < 2 && p.fast; ++l) {
+        p.upcat_w[l] = a.take(smirk_conv3x3_upcat_weff_bytes(f << l));
+        p.upcat_s[l] = a.take(smirk_conv3x3_upcat_shift_bytes(f << l));
+    }
+    for (int l = 2; l < 4 && p.fast; ++l) {
+        p.updeep_w[l - 2] = a.take(smirk_updeep_weff_bytes(f << l));
+        p.updeep_s[l - 2] = a.take(smirk_updeep_shift_bytes(f << l));
+        p.updeep_k[l - 2] = a.take(smirk_updeep_wskip_bytes(f << l));
+    }
+    r.workspace_bytes = smirk_align_up(a.off, 256);
+    return p;
+}
+
+// ---- the emitters: one level's launches on `nb` frames, every pointer already resolved by the caller (whole-batch tensors, or a chain's views) -----------------------
+int pool2x2(bool split, const void* in, void* out, int nb, int h, int wd, int c, void* strm) {
+    return split ? smirk_maxpool2x2_split16(in, out, nb, h, wd, c, strm) : smirk_maxpool2x2_nhwc((const float*)in, (float*)out, nb, h, wd, c, strm);
+}
+
+void tap_copy(void* tap, const void* src, size_t bytes, void* strm) {
+    if (tap) (void)hipMemcpyAsync(tap, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)strm);
+}
+
+// the slots an encoder level writes, in the order the families have always picked them (which slot a tensor lands in is part of "same bits, same overlap")
+void encoder_slots(const Rot& rot, int family, const void* in, void*& t1, void*& pooled) {
+    t1 = family == SMIRK_GEN_ENC_ENC1_FUSED ? nullptr : rot.pick(in, nullptr);
+    pooled = family == SMIRK_GEN_ENC_CONV_POOLFUSED ? rot.pick(t1, nullptr) : rot.pick(nullptr, nullptr);
+}
+
+// encoder level l (smirk_generator.py:52-59): in [h][wd][cin] -> conv -> t1 -> conv -> skip [h][wd][c] -> pool -> pooled
+int encoder_level(const SmirkGeneratorWeights* w, int family, int l, int nb, int h, int wd, int cin, const void* in, void* t1, void* skip, void* pooled, void* tap,
+                  void* strm) {
+    const bool split = w->precision == SMIRK_PRECISION_F16X3;
+    const int c = w->features << l;
+    const SmirkConvLayer *c1 = &w->enc[l][0], *c2 = &w->enc[l][1];
+    const SmirkConvDesc d1 = desc3x3(nb, h, wd, cin, 0, c, false, true), d2 = desc3x3(nb, h, wd, c, 0, c, false, true);
+    switch (family) {
+        case SMIRK_GEN_ENC_ENC1_FUSED:
+            TRY(smirk_enc1_fused_split16(in, c1->w, c1->scale, c1->shift, c2->w, c2->scale, c2->shift, skip, pooled, nb, h, wd, strm));
+            break;
+        case SMIRK_GEN_ENC_CONV_POOLFUSED:
+            TRY(conv_call(split, d1, in, nullptr, *c1, nullptr, t1, strm));
+            TRY(smirk_conv3x3_pool_f16x3(&d2, t1, nullptr, c2->w, c2->scale, c2->shift, skip, pooled, strm));
+            break;
+        default:                                                    // SMIRK_GEN_ENC_CONV_CONV_POOL
+            TRY(conv_call(split, d1, in, nullptr, *c1, nullptr, t1, strm));
+            TRY(conv_call(split, d2, t1, nullptr, *c2, nullptr, skip, strm));
+            break;
+    }
+    tap_copy(tap, skip, act_bytes(nb, h, wd, c), strm);
+    return family == SMIRK_GEN_ENC_CONV_CONV_POOL ? pool2x2(split, skip, pooled, nb, h, wd, c, strm) : SMIRK_OK;
+}
+
+SmirkUpdeepLevel updeep_level(const SmirkGeneratorWeights* w, const GenPlan& p, int l) {
+    return SmirkUpdeepLevel{w->features << l, &w->up[3 - l], &w->dec[3 - l][0], p.updeep_w[l - 2], p.updeep_s[l - 2], p.updeep_k[l - 2]};
+}
+
+void decoder_slots(const Rot& rot, int family, const void* coarse, void*& tmp, void*& out) {
+    tmp = family == SMIRK_GEN_DEC_UPCAT ? nullptr : rot.pick(coarse, nullptr);
+    out = rot.pick(family == SMIRK_GEN_DEC_UPCAT ? coarse : tmp, nullptr);
+}
+
+// the first half of decoder level l (smirk_generator.py:65-75): ConvTranspose2d k2 s2 of coarse [h/2][wd/2][2c], cat with skip [h][wd][c], conv -> out [h][wd][c];
+// tmp holds `up` (PAIR) or the coarse launch's partial sums (UPDEEP)
+int decoder_level(const SmirkGeneratorWeights* w, const GenPlan& p, int family, int l, int nb, int h, int wd, const void* coarse, const void* skip, void* tmp,
+                  void* out, void* strm) {
+    const bool split = w->precision == SMIRK_PRECISION_F16X3;
+    const int c = w->features << l;
+    const SmirkConvLayer &up = w->up[3 - l], &conv = w->dec[3 - l][0];
+    switch (family) {
+        case SMIRK_GEN_DEC_UPCAT:
+            return smirk_conv3x3_upcat_launch(c, coarse, skip, &up, &conv, out, nb, h, wd, p.upcat_w[l], p.upcat_s[l], (hipStream_t)strm);
+        case SMIRK_GEN_DEC_UPDEEP: {                                // launch 2 is the ordinary 3x3 convolution over the skip tensor with launch 1's output as its residual
+            const SmirkUpdeepLevel u = updeep_level(w, p, l);
+            TRY(smirk_updeep_coarse_launch(&u, coarse, tmp, nb, h, wd, (hipStream_t)strm));
+            const SmirkConvLayer half{u.wskip, conv.scale, conv.shift};
+            return conv_call(true, desc3x3(nb, h, wd, c, 0, c, false, true), skip, nullptr, half, tmp, out, strm);
+        }
+        default:                                                    // SMIRK_GEN_DEC_PAIR
+            TRY(conv_call(split, desc1x1(nb, h / 2, wd / 2, 2 * c, c, false, true), coarse, nullptr, up, nullptr, tmp, strm));
+            return conv_call(split, desc3x3(nb, h, wd, c, c, c, false, true), tmp, skip, conv, nullptr, out, strm);
+    }
+}
+
 }  // namespace
 
 extern "C" size_t smirk_generator_workspace_bytes(const SmirkGeneratorWeights* w, int B, int H, int W) {
     if (!gen_args_ok(w, B, H, W)) return 0;
-    return plan_generator(w, B, H, W, nullptr).total;
+    return plan_generator(w, 0, 0, B, H, W, false, 1, nullptr).r.workspace_bytes;
 }
 
-// The one body of the two whole-network entries: smirk_generator_forward packs cat(a, b) into the workspace first, smirk_generator_forward_packed
-// (include/smirk_handoff.h) hands in `packed`, the same tensor written by masking_handoff_kernel, and the pack step is left out.
+extern "C" int smirk_genplan_abi_version(void) { return SMIRK_GENPLAN_ABI_VERSION; }
+
+extern "C" int smirk_generator_plan(const SmirkGeneratorWeights* w, int Ca, int Cb, int B, int H, int W, int with_taps, SmirkGeneratorPlanReport* report) {
+    if (!gen_args_ok(w, B, H, W) || !report) return SMIRK_ERR_BAD_ARG;
+    const bool packed = Ca == 0 && Cb == 0;
+    if (packed ? w->precision != SMIRK_PRECISION_F16X3 : (Ca <= 0 || Cb < 0 || Ca + Cb != w->in_channels)) return SMIRK_ERR_BAD_ARG;
+    *report = plan_generator(w, Ca, Cb, B, H, W, with_taps != 0, gen_chain_wish(w, B, H, W, with_taps != 0), nullptr).r;
+    return report->input < 0 ? SMIRK_ERR_UNSUPPORTED : SMIRK_OK;
+}
+
+// The one body of the two whole-network entries, a walk over the plan: smirk_generator_forward packs cat(a, b) into the workspace first,
+// smirk_generator_forward_packed (include/smirk_handoff.h) hands in `packed`, the same tensor written by masking_handoff_kernel, and the pack step is left out.
 static int generator_forward_body(const SmirkGeneratorWeights* w, const float* a, int Ca, const float* b, int Cb, const void* packed, float* y, int B, int H,
                                   int W, void* const* taps, void* ws, size_t ws_bytes, void* stream) {
-    const GenPlan p = plan_generator(w, B, H, W, ws);
-    if (ws_bytes < p.total) return SMIRK_ERR_WORKSPACE;
+    const int wish = gen_chain_wish(w, B, H, W, taps != nullptr);
+    GenPlan p = plan_generator(w, Ca, Cb, B, H, W, taps != nullptr, wish, ws);
+    if (ws_bytes < p.r.workspace_bytes) return SMIRK_ERR_WORKSPACE;
+    if (p.r.input < 0) return SMIRK_ERR_UNSUPPORTED;
+    const ChainGrant cg = grant_chains(wish, (hipStream_t)stream);
+    if (cg.n != wish) p = plan_generator(w, Ca, Cb, B, H, W, taps != nullptr, cg.n, ws);
+    const SmirkGeneratorPlanReport& r = p.r;
     const bool split = w->precision == SMIRK_PRECISION_F16X3;
-    const int f = w->features;
+    const int f = w->features, L0 = GEN_SECTION_FROM;
+    auto tap = [&](int i) { return taps ? taps[i] : nullptr; };
 
-    // ---- cat + NCHW -> NHWC (+ split) of the network input (smirk_trainer.py:94, demo.py:167) ----------------------------------------
-    if (packed) {
-        // already in the network's input format
-    } else if (split) {
-        TRY(smirk_pack_generator_input_split16(a, Ca, b, Cb, p.x, B, H, W, stream));
-    } else if (Cb == 0) {
-        TRY(smirk_nchw_to_nhwc_pad(a, (float*)p.x, B, Ca, H, W, w->cin_pad, stream));
-    } else {
-        if (Ca != 3 || Cb != 3 || w->cin_pad != 8) return SMIRK_ERR_UNSUPPORTED;
-        TRY(smirk_pack_generator_input(a, b, (float*)p.x, B, H, W, stream));
+    // ---- cat + NCHW -> NHWC (+ split) of the network input (smirk_trainer.py:94, demo.py:167), and the composed weights of the deep decoder levels ------------------
+    switch (r.input) {
+        case SMIRK_GEN_INPUT_PACKED: break;                         // already in the network's input format
+        case SMIRK_GEN_INPUT_SPLIT_PACK: TRY(smirk_pack_generator_input_split16(a, Ca, b, Cb, p.x, B, H, W, stream)); break;
+        case SMIRK_GEN_INPUT_NHWC_PAD: TRY(smirk_nchw_to_nhwc_pad(a, (float*)p.x, B, Ca, H, W, w->cin_pad, stream)); break;
+        default: TRY(smirk_pack_generator_input(a, b, (float*)p.x, B, H, W, stream)); break;
     }
-    // ---- decoder levels 3 / 4 (l = 2, 3): the ConvTranspose composed into the level's first convolution as two launches (conv_halo.hip) where
-    // conv_halo takes both; their weights are composed by ONE launch here, on the caller's stream ahead of the fork event, so that every sub-batch chain reads them.
-    // A chain decides again with its own frame count (ud_on says whether the weights exist).  $SMIRK_IGEMM_HALO=0 restores the two-launch levels.
-    SmirkUpdeepLevel ud[2];
-    bool ud_on[2] = {false, false};
-    {
+    if (r.compose_mask) {
         SmirkUpdeepLevel todo[2];
         int n = 0;
-        for (int l = 2; l < 4; ++l) {
-            ud[l - 2] = SmirkUpdeepLevel{f << l, &w->up[3 - l], &w->dec[3 - l][0], p.updeep_w[l - 2], p.updeep_s[l - 2], p.updeep_k[l - 2]};
-            ud_on[l - 2] = split && f == 32 && smirk_updeep_eligible(B, H >> l, W >> l, f << l);
-            if (ud_on[l - 2]) todo[n++] = ud[l - 2];
-        }
-        if (n) TRY(smirk_updeep_compose(todo, n, (hipStream_t)stream));
+        for (int l = 2; l < 4; ++l)
+            if (r.compose_mask & (1 << l)) todo[n++] = updeep_level(w, p, l);
+        TRY(smirk_updeep_compose(todo, n, (hipStream_t)stream));
     }
-    // launch 1 writes partial' where `up` used to go; launch 2 is the ordinary 3x3 convolution over the skip tensor with partial' as its residual
-    auto updeep = [&](int l, int nb, int h, int wd, const void* coarse, const void* skip, void* partial, void* out, void* strm) -> int {
-        const SmirkUpdeepLevel& u = ud[l - 2];
-        TRY(smirk_updeep_coarse_launch(&u, coarse, partial, nb, h, wd, (hipStream_t)strm));
-        const SmirkConvLayer half{u.wskip, u.conv->scale, u.conv->shift};
-        return conv_call(true, desc3x3(nb, h, wd, u.c, 0, u.c, false, true), skip, nullptr, half, partial, out, strm);
-    };
-    auto pool = [&](const void* in, void* out, int h, int wd, int c) {
-        return split ? smirk_maxpool2x2_split16(in, out, B, h, wd, c, stream) : smirk_maxpool2x2_nhwc((const float*)in, (float*)out, B, h, wd, c, stream);
-    };
-    auto tap = [&](int i, const void* src, size_t bytes) {
-        if (taps && taps[i]) (void)hipMemcpyAsync(taps[i], src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-    };
-
-    // ---- how the deep part of the network is launched (decided first: it sets where the whole-batch launches stop) ---------------------------------------------
-    // The layers at H/4 and below rarely fill whole rounds of workgroups on the 256 CUs (14 x 14 x 512: 196 B / 256 tiles x 4 = 1.53 rounds at 128 frames = 2 rounds
-    // of time, 3.06 -> 4 at 256; the 28 x 28 and 56 x 56 layers likewise), and each waits for the one before it.  Frames are independent, so this SECTION — encoder3,
-    // encoder4, bottleneck, ResNet blocks, decoder4, decoder3 — runs as TWO (optionally three) sub-batch chains on as many streams (the caller's and library-owned
-    // side streams, forked / joined with events): while one chain's layer drains its partial last round the other chain's workgroups take the free CUs.
-    // Bit-identical results (batch invariance, tests/test_scale_gpu.py run with it forced).  Measured with the RCCL gather enqueued, same box (profiles/r04l_, r04m_,
-    // r04n_): +3.2 % at 128 frames per pass, +4.5 % at 256, +1.2 % at 1024 for the H/8 + H/16 part -> taken when > 5 % of a 14 x 14 layer's last round would idle.
-    // $SMIRK_GEN_SPLIT_CHAINS=0 / 2 / 3 selects the number of chains (the A/B switch of tests/test_generator_gpu.py).  The section starts at H/8: starting it at H/4
-    // measured 8,801 vs 8,857 faces/s at 128 frames, 9,406 vs 9,473 at 256, 9,872 vs 9,782 at 1024 (profiles/r04n_chain_from.txt; the 56 x 56 layers fill their rounds) and
-    // the switch for it left the library.  Batches below 16 frames are never split by the heuristic (a fork / join costs more than the idle part of their only round).
-    const int h16 = H >> 4, w16 = W >> 4, c16 = f << 4;
-    const int L0 = 3;
-    int nchain = 1;
-    if (B >= 2 && !taps && !g_smirk_prof_on) {                      // (taps copy whole tensors; the launch profiler times launches on ONE stream)
-        const double rounds = ((double)B * h16 * w16 / 256.0) * (c16 / 128.0) / smirk_device_cus();      // 256 x 128 tiles of a 14 x 14 layer per CU
-        const double full = (double)(long long)(rounds + 0.999999);
-        if (B >= 16 && full > 0 && (full - rounds) / full > 0.05) nchain = 2;
-        if (const int forced = smirk_switch(SMIRK_SW_GEN_SPLIT_CHAINS)) nchain = forced;
-        if (nchain > B) nchain = B;
-    }
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (nchain > 1 && (hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)) { (void)hipGetLastError(); nchain = 1; }
-    // Side streams and the fork / join events are owned per HOST THREAD and device (thread_local): two threads driving the same device neither race on the lazy
-    // creation nor record / wait on each other's events; created once, reused by every forward of that thread (re-recording an event only affects later waits).
-    hipStream_t side[2] = {nullptr, nullptr};
-    hipEvent_t fork = nullptr, join[2] = {nullptr, nullptr};
-    if (nchain > 1) {
-        // RAII: a host thread that ends releases its side streams and events (a thread pool of short-lived workers leaked 2 streams + 3 events per thread; advisor r05).
-        // The destructor runs at thread exit; work still queued on a side stream completes first (hipStreamDestroy defers the release until the stream drains).
-        struct ChainResources {
-            hipStream_t side[64][2] = {};
-            hipEvent_t ev[64][3] = {};
-            ~ChainResources() {
-                // the MAIN thread's thread_locals are destroyed inside exit(), where the HIP runtime may already be shutting down: the process exit reclaims them
-                if ((long)syscall(SYS_gettid) == (long)getpid()) return;
-                int cur = 0;
-                const bool have = hipGetDevice(&cur) == hipSuccess;
-                for (int d = 0; d < 64; ++d) {
-                    bool any = false;
-                    for (int k = 0; k < 2; ++k) any = any || side[d][k];
-                    for (int k = 0; k < 3; ++k) any = any || ev[d][k];
-                    if (!any) continue;
-                    if (hipSetDevice(d) != hipSuccess) { (void)hipGetLastError(); continue; }
-                    for (int k = 0; k < 2; ++k) if (side[d][k]) (void)hipStreamDestroy(side[d][k]);
-                    for (int k = 0; k < 3; ++k) if (ev[d][k]) (void)hipEventDestroy(ev[d][k]);
-                }
-                if (have) (void)hipSetDevice(cur);
-                (void)hipGetLastError();
-            }
-        };
-        thread_local ChainResources chain_res;
-        hipStream_t (&side_dev)[64][2] = chain_res.side;
-        hipEvent_t (&ev_dev)[64][3] = chain_res.ev;
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); nchain = 1; }
-        else {
-            for (int k = 0; k < 3 && nchain > 1; ++k)
-                if (!ev_dev[dev][k] && hipEventCreateWithFlags(&ev_dev[dev][k], hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); ev_dev[dev][k] = nullptr; nchain = 1; }
-            for (int k = 0; k + 1 < nchain; ++k) {
-                if (!side_dev[dev][k] && hipStreamCreateWithFlags(&side_dev[dev][k], hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); side_dev[dev][k] = nullptr; nchain = 1; break; }
-                side[k] = side_dev[dev][k];
-            }
-            fork = ev_dev[dev][0]; join[0] = ev_dev[dev][1]; join[1] = ev_dev[dev][2];
-        }
-    }
-    // ---- encoder levels above the section, whole batch (smirk_generator.py:52-57) --------------------------------------------------------------------------
+    // ---- encoder levels above the section, whole batch --------------------------------------------------------------------------------------------------------------
     const void* cur = packed ? packed : p.x;
-    int cin = w->cin_pad;
     for (int l = 0; l < L0; ++l) {
-        const int h = H >> l, wd = W >> l, c = f << l;
-        if (l == 0 && split && smirk_enc1_fused_supported(cin, f, h, wd)) {
-            // encoder1 + pool1 in one launch (enc1_fused.hip): the 32-channel full-resolution tensor between the two convolutions never reaches HBM
-            void* pl = p.rot.pick(nullptr, nullptr);
-            TRY(smirk_enc1_fused_split16(cur, w->enc[0][0].w, w->enc[0][0].scale, w->enc[0][0].shift, w->enc[0][1].w, w->enc[0][1].scale,
-                                         w->enc[0][1].shift, p.e[0], pl, B, h, wd, stream));
-            tap(0, p.e[0], act_bytes(B, h, wd, c));
-            cur = pl;
-            cin = c;
-            continue;
-        }
-        void* t1 = p.rot.pick(cur, nullptr);
-        TRY(conv_call(split, desc3x3(B, h, wd, cin, 0, c, false, true), cur, nullptr, w->enc[l][0], nullptr, t1, stream));
-        void* t2 = p.e[l];
-        if (split) {                                       // conv2 + BN + ReLU + pool in one launch where a kernel with a fused pool serves the shape
-            void* pl = p.rot.pick(t1, nullptr);
-            const SmirkConvDesc d2 = desc3x3(B, h, wd, c, 0, c, false, true);
-            const int rc = smirk_conv3x3_pool_f16x3(&d2, t1, nullptr, w->enc[l][1].w, w->enc[l][1].scale, w->enc[l][1].shift, t2, pl, stream);
-            if (rc == SMIRK_OK) {
-                tap(l, t2, act_bytes(B, h, wd, c));
-                cur = pl;
-                cin = c;
-                continue;
-            }
-            if (rc != SMIRK_ERR_UNSUPPORTED) return rc;
-        }
-        TRY(conv_call(split, desc3x3(B, h, wd, c, 0, c, false, true), t1, nullptr, w->enc[l][1], nullptr, t2, stream));
-        tap(l, t2, act_bytes(B, h, wd, c));
-        void* pl = p.rot.pick(nullptr, nullptr);
-        TRY(pool(t2, pl, h, wd, c));
+        void *t1, *pl;
+        encoder_slots(p.rot, r.enc[l], cur, t1, pl);
+        TRY(encoder_level(w, r.enc[l], l, B, H >> l, W >> l, l ? f << (l - 1) : w->cin_pad, cur, t1, p.e[l], pl, tap(l), stream));
         cur = pl;
-        cin = c;
     }
-    // ---- the section (smirk_generator.py:56-68, :121-178) -----------------------------------------------------------------------------------------------
+    // ---- the section (smirk_generator.py:56-68, :121-178), once per chain ---------------------------------------------------------------------------------------------
     // Memory: temporaries rotate through the three scratch slots, each sized for the largest tensor of the network (B x H x W x f elements = 4x the largest tensor of
     // this section).  The chains run at different paces and would otherwise put tensors of DIFFERENT shapes (so different frame offsets) into one slot at the same
     // time: chain k keeps its temporaries in QUARTER k + 1 of every slot, indexed from frame 0; only the tensors that cross the section's boundary use the whole-batch
     // layout — its input (the pooled tensor of the level above), the skip tensors, its output — which all lie inside quarter 0 with frame ranges that are disjoint
     // between the chains; the output never shares a slot with the input (one chain may finish while another still reads its input frames).
     const size_t quarter = (act_bytes(B, H, W, f) / 4) & ~(size_t)255;
-    auto poolh = [&](const void* in, void* out, int nb, int h, int wd, int c, void* strm) {
-        return split ? smirk_maxpool2x2_split16(in, out, nb, h, wd, c, strm) : smirk_maxpool2x2_nhwc((const float*)in, (float*)out, nb, h, wd, c, strm);
-    };
-    auto deep = [&](int chain, int b0, int nb, void* strm, const void* in, const void*& out) -> int {
-        const size_t priv = nchain > 1 ? quarter * (size_t)(chain + 1) : 0;
-        auto N = [&](const void* base, int h, int wd, int c) { return (const void*)((const char*)base + act_bytes(b0, h, wd, c)); };    // whole-batch layout
-        auto Nw = [&](void* base, int h, int wd, int c) { return (void*)((char*)base + act_bytes(b0, h, wd, c)); };
-        auto P = [&](const void* base) { return (const void*)((const char*)base + priv); };                                              // chain-private
-        auto Pw = [&](void* base) { return (void*)((char*)base + priv); };
-        const void* cur = in;
-        bool cur_nat = true;
-        int ci = f << (L0 - 1);
-        for (int l = L0; l < 4; ++l) {                              // encoder levels of the section: conv, conv -> skip tensor, pool
+    const int h16 = H >> 4, w16 = W >> 4, c16 = f << 4;
+    auto section = [&](int k, void* strm, const void* in, const void*& out) -> int {
+        const int b0 = r.chain_b0[k], nb = r.chain_nb[k];
+        const size_t priv = r.nchain > 1 ? quarter * (size_t)(k + 1) : 0;
+        auto N = [&](const void* base, int h, int wd, int c) { return (char*)base + act_bytes(b0, h, wd, c); };     // this chain's frames of a whole-batch tensor
+        auto P = [&](const void* base) { return (char*)base + priv; };                                               // a chain-private temporary
+        const void* cur = N(in, H >> L0, W >> L0, f << (L0 - 1));
+        const void* cur_slot = in;
+        for (int l = L0; l < 4; ++l) {
             const int h = H >> l, wd = W >> l, c = f << l;
-            void* t1 = p.rot.pick(cur, nullptr);
-            TRY(conv_call(split, desc3x3(nb, h, wd, ci, 0, c, false, true), cur_nat ? N(cur, h, wd, ci) : P(cur), nullptr, w->enc[l][0], nullptr, Pw(t1), strm));
-            TRY(conv_call(split, desc3x3(nb, h, wd, c, 0, c, false, true), P(t1), nullptr, w->enc[l][1], nullptr, Nw(p.e[l], h, wd, c), strm));
-            tap(l, p.e[l], act_bytes(B, h, wd, c));                 // (taps => one chain over the whole batch on the caller's stream)
-            void* pl = p.rot.pick(nullptr, nullptr);
-            TRY(poolh(N(p.e[l], h, wd, c), Pw(pl), nb, h, wd, c, strm));
-            cur = pl; cur_nat = false; ci = c;
+            void *t1, *pl;
+            encoder_slots(p.rot, r.enc[l], cur_slot, t1, pl);
+            TRY(encoder_level(w, r.enc[l], l, nb, h, wd, c / 2, cur, P(t1), N(p.e[l], h, wd, c), P(pl), tap(l), strm));   // (taps => one chain over the whole batch)
+            cur = P(pl); cur_slot = pl;
         }
-        const int c8 = f << 3;
-        void* b1 = p.rot.pick(cur, nullptr);                        // bottleneck
-        TRY(conv_call(split, desc3x3(nb, h16, w16, c8, 0, c16, false, true), P(cur), nullptr, w->enc[4][0], nullptr, Pw(b1), strm));
+        void* b1 = p.rot.pick(cur_slot, nullptr);                   // bottleneck
+        TRY(conv_call(split, desc3x3(nb, h16, w16, c16 / 2, 0, c16, false, true), cur, nullptr, w->enc[4][0], nullptr, P(b1), strm));
         void* b2 = p.rot.pick(b1, nullptr);
-        TRY(conv_call(split, desc3x3(nb, h16, w16, c16, 0, c16, false, true), P(b1), nullptr, w->enc[4][1], nullptr, Pw(b2), strm));
-        tap(4, b2, act_bytes(B, h16, w16, c16));
-        const void* cur16 = b2;                                     // ResNet blocks: reflect pad, conv-BN-ReLU, reflect pad, conv-BN, + x
-        for (int k = 0; k < w->res_blocks; ++k) {
-            void* t = p.rot.pick(cur16, nullptr);
-            TRY(conv_call(split, desc3x3(nb, h16, w16, c16, 0, c16, true, true), P(cur16), nullptr, w->res[k][0], nullptr, Pw(t), strm));
-            void* o = p.rot.pick(cur16, t);
-            TRY(conv_call(split, desc3x3(nb, h16, w16, c16, 0, c16, true, false), P(t), nullptr, w->res[k][1], P(cur16), Pw(o), strm));
-            cur16 = o;
+        TRY(conv_call(split, desc3x3(nb, h16, w16, c16, 0, c16, false, true), P(b1), nullptr, w->enc[4][1], nullptr, P(b2), strm));
+        tap_copy(tap(4), b2, act_bytes(B, h16, w16, c16), strm);
+        const void* dc = b2;                                        // ResNet blocks: reflect pad, conv-BN-ReLU, reflect pad, conv-BN, + x
+        for (int i = 0; i < w->res_blocks; ++i) {
+            void* t = p.rot.pick(dc, nullptr);
+            TRY(conv_call(split, desc3x3(nb, h16, w16, c16, 0, c16, true, true), P(dc), nullptr, w->res[i][0], nullptr, P(t), strm));
+            void* o = p.rot.pick(dc, t);
+            TRY(conv_call(split, desc3x3(nb, h16, w16, c16, 0, c16, true, false), P(t), nullptr, w->res[i][1], P(dc), P(o), strm));
+            dc = o;
         }
-        tap(5, cur16, act_bytes(B, h16, w16, c16));
-        const void* dc = cur16;
-        for (int l = 3; l >= L0; --l) {                             // decoder levels of the section: ConvTranspose2d, two-source conv with the skip, conv
+        tap_copy(tap(5), dc, act_bytes(B, h16, w16, c16), strm);
+        for (int l = 3; l >= L0; --l) {                             // decoder levels of the section; the last one writes the whole-batch layout
             const int h = H >> l, wd = W >> l, c = f << l;
-            void* up = p.rot.pick(dc, nullptr);                     // (composed level: partial')
-            void* d1 = p.rot.pick(up, nullptr);
-            if (ud_on[l - 2] && smirk_updeep_eligible(nb, h, wd, c)) {
-                TRY(updeep(l, nb, h, wd, P(dc), N(p.e[l], h, wd, c), Pw(up), Pw(d1), strm));
-            } else {
-                TRY(conv_call(split, desc1x1(nb, h / 2, wd / 2, 2 * c, c, false, true), P(dc), nullptr, w->up[3 - l], nullptr, Pw(up), strm));
-                TRY(conv_call(split, desc3x3(nb, h, wd, c, c, c, false, true), P(up), N(p.e[l], h, wd, c), w->dec[3 - l][0], nullptr, Pw(d1), strm));
-            }
+            void *tmp, *d1;
+            decoder_slots(p.rot, r.dec[l][k], dc, tmp, d1);
+            TRY(decoder_level(w, p, r.dec[l][k], l, nb, h, wd, P(dc), N(p.e[l], h, wd, c), P(tmp), P(d1), strm));
             const bool last = l == L0;
             void* d2 = last ? p.rot.pick(d1, in) : p.rot.pick(d1, nullptr);
-            TRY(conv_call(split, desc3x3(nb, h, wd, c, 0, c, false, true), P(d1), nullptr, w->dec[3 - l][1], nullptr, last ? Nw(d2, h, wd, c) : Pw(d2), strm));
-            tap(6 + (3 - l), d2, act_bytes(B, h, wd, c));
+            TRY(conv_call(split, desc3x3(nb, h, wd, c, 0, c, false, true), P(d1), nullptr, w->dec[3 - l][1], nullptr, last ? N(d2, h, wd, c) : P(d2), strm));
+            tap_copy(tap(6 + (3 - l)), d2, act_bytes(B, h, wd, c), strm);
             dc = d2;
         }
         out = dc;
         return SMIRK_OK;
     };
     const void* dcur = nullptr;
-    if (nchain > 1) {
-        int rc = hipEventRecord(fork, (hipStream_t)stream) == hipSuccess ? SMIRK_OK : SMIRK_ERR_LAUNCH;
-        const void* last = nullptr;
+    if (r.nchain > 1) {
+        int rc = hipEventRecord(cg.fork, (hipStream_t)stream) == hipSuccess ? SMIRK_OK : SMIRK_ERR_LAUNCH;
         bool forked[2] = {false, false};
-        for (int k = nchain - 1; rc == SMIRK_OK && k >= 0; --k) {   // chain k owns frames [B k / n, B (k+1) / n); chain 0 runs on the caller's stream, enqueued last
-            const int b0 = (int)((long long)B * k / nchain), b1 = (int)((long long)B * (k + 1) / nchain);
-            hipStream_t st_k = k == 0 ? (hipStream_t)stream : side[k - 1];
-            if (k > 0 && hipStreamWaitEvent(st_k, fork, 0) != hipSuccess) { rc = SMIRK_ERR_LAUNCH; break; }
+        for (int k = r.nchain - 1; rc == SMIRK_OK && k >= 0; --k) {   // chain 0 runs on the caller's stream, enqueued last
+            hipStream_t st_k = k == 0 ? (hipStream_t)stream : cg.side[k - 1];
+            if (k > 0 && hipStreamWaitEvent(st_k, cg.fork, 0) != hipSuccess) { rc = SMIRK_ERR_LAUNCH; break; }
             if (k > 0) forked[k - 1] = true;
-            rc = deep(k, b0, b1 - b0, (void*)st_k, cur, last);
-            if (rc == SMIRK_OK && k > 0 && hipEventRecord(join[k - 1], st_k) != hipSuccess) rc = SMIRK_ERR_LAUNCH;
+            rc = section(k, (void*)st_k, cur, dcur);
+            if (rc == SMIRK_OK && k > 0 && hipEventRecord(cg.join[k - 1], st_k) != hipSuccess) rc = SMIRK_ERR_LAUNCH;
         }
-        for (int k = 0; rc == SMIRK_OK && k + 1 < nchain; ++k)
-            if (hipStreamWaitEvent((hipStream_t)stream, join[k], 0) != hipSuccess) rc = SMIRK_ERR_LAUNCH;
+        for (int k = 0; rc == SMIRK_OK && k + 1 < r.nchain; ++k)
+            if (hipStreamWaitEvent((hipStream_t)stream, cg.join[k], 0) != hipSuccess) rc = SMIRK_ERR_LAUNCH;
         if (rc != SMIRK_OK) {
             // a chain failed part-way: whatever was enqueued on the side streams still reads / writes the caller's workspace.  The caller's stream must not run
             // ahead of it (the workspace may be reused or freed in stream order), so the side streams are drained before the error is returned.
             for (int k = 0; k < 2; ++k)
-                if (forked[k]) (void)hipStreamSynchronize(side[k]);
+                if (forked[k]) (void)hipStreamSynchronize(cg.side[k]);
             return rc;
         }
-        dcur = last;
     } else {
-        TRY(deep(0, 0, B, stream, cur, dcur));
+        TRY(section(0, stream, cur, dcur));
     }
-    // ---- decoder4..1 (smirk_generator.py:65-75): ConvTranspose2d k2 s2, cat with the skip (two-source conv), double conv -------------------
-    for (int l = L0 - 1; l >= 0; --l) {                              // decoder levels above the section, whole batch
+    // ---- decoder levels above the section, whole batch, and the network tail ----------------------------------------------------------------------------------------
+    for (int l = L0 - 1; l >= 0; --l) {
         const int h = H >> l, wd = W >> l, c = f << l;              // output resolution of this level
-        void* t1;
-        if (l < 2 && split && f == 32 && smirk_conv3x3_upcat_eligible(c, h, wd)) {
-            // levels 1 / 2: the ConvTranspose composed into the convolution that reads it (conv_upcat.hip) — no `up` tensor; $SMIRK_CONV_RING=0 restores the two launches
-            t1 = p.rot.pick(dcur, nullptr);
-            TRY(smirk_conv3x3_upcat_launch(c, dcur, p.e[l], &w->up[3 - l], &w->dec[3 - l][0], t1, B, h, wd, p.upcat_w[l], p.upcat_s[l], (hipStream_t)stream));
-        } else if (l >= 2 && ud_on[l - 2]) {
-            // level 3: the ConvTranspose composed into the convolution as two launches (above) — no `up` tensor; $SMIRK_IGEMM_HALO=0 restores the old pair
-            void* pp = p.rot.pick(dcur, nullptr);
-            t1 = p.rot.pick(pp, nullptr);
-            TRY(updeep(l, B, h, wd, dcur, p.e[l], pp, t1, stream));
-        } else {
-            void* up = p.rot.pick(dcur, nullptr);
-            TRY(conv_call(split, desc1x1(B, h / 2, wd / 2, 2 * c, c, false, true), dcur, nullptr, w->up[3 - l], nullptr, up, stream));
-            t1 = p.rot.pick(up, nullptr);
-            TRY(conv_call(split, desc3x3(B, h, wd, c, c, c, false, true), up, p.e[l], w->dec[3 - l][0], nullptr, t1, stream));
-        }
-        if (l == 0 && split && !taps && f == 32 && H >= 64) {
-            // network tail in one launch: dec1conv2 + BN + ReLU + final 1x1 conv + sigmoid (dec1 never reaches HBM)
-            SmirkConvDesc d = desc3x3(B, h, wd, c, 0, c, false, true);
-            const int rc = smirk_conv3x3_tail_f16x3(&d, t1, nullptr, w->dec[3][1].w, w->dec[3][1].scale, w->dec[3][1].shift, w->final_w, w->final_b,
-                                                    y, w->out_channels, stream);
-            if (rc != SMIRK_ERR_UNSUPPORTED) return rc;
-        }
+        void *tmp, *t1;
+        decoder_slots(p.rot, r.dec[l][0], dcur, tmp, t1);
+        TRY(decoder_level(w, p, r.dec[l][0], l, B, h, wd, dcur, p.e[l], tmp, t1, stream));
+        const SmirkConvLayer& c2 = w->dec[3 - l][1];
+        const SmirkConvDesc d2 = desc3x3(B, h, wd, c, 0, c, false, true);
+        if (l == 0 && r.fused_tail) return smirk_conv3x3_tail_f16x3(&d2, t1, nullptr, c2.w, c2.scale, c2.shift, w->final_w, w->final_b, y, w->out_channels, stream);
         void* t2 = p.rot.pick(t1, nullptr);
-        TRY(conv_call(split, desc3x3(B, h, wd, c, 0, c, false, true), t1, nullptr, w->dec[3 - l][1], nullptr, t2, stream));
-        tap(6 + (3 - l), t2, act_bytes(B, h, wd, c));
+        TRY(conv_call(split, d2, t1, nullptr, c2, nullptr, t2, stream));
+        tap_copy(tap(6 + (3 - l)), t2, act_bytes(B, h, wd, c), stream);
         dcur = t2;
     }
     return split ? smirk_conv1x1_sigmoid_nchw_split16(dcur, w->final_w, w->final_b, y, B, H, W, f, w->out_channels, stream)
