@@ -416,7 +416,7 @@ int smirk_backbone_forward(const SmirkBackboneWeights* w, const float* img, int 
 enum SmirkBackboneFamily {
     SMIRK_BACKBONE_HEAD_FUSED = 0,  /* stem + first DepthwiseSeparable block: smirk_encoder_head_fused_split16                      */
     SMIRK_BACKBONE_CONV1X1 = 1,     /* ConvBnAct 1x1: smirk_conv_igemm_*                                                            */
-    SMIRK_BACKBONE_MBCONV_IMAGE = 2,/* smirk_mbconv_image_split16: 14 x 14 halo tiles or whole images per workgroup                 */
+    SMIRK_BACKBONE_MBCONV_IMAGE = 2,/* smirk_mbconv_image_split16: one wave per 2 x 14 halo band, or whole images per workgroup  */
     SMIRK_BACKBONE_MBCONV_S2 = 3,   /* smirk_mbconv_s2_split16: stride 2, one wave per output tile                                  */
     SMIRK_BACKBONE_MBCONV_TILE = 4, /* smirk_mbconv_fused_split16: 8 x 8 output tiles (the fallback of the two above)               */
     SMIRK_BACKBONE_DS_UNFUSED = 5,  /* DepthwiseSeparable as depthwise + pointwise launches                                         */

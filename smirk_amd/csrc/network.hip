@@ -486,7 +486,7 @@ BackboneSwitches backbone_switches() {
 // backbones takes).  Rows 2-4 are for InvertedResidual blocks in the split-fp16 precision, unless $SMIRK_DISABLE_MBCONV_FUSED; each `*_supported` is the kernel's own
 // statement of what it serves and is not restated here.
 //   1  CONV1X1        ConvBnAct 1x1: one implicit-GEMM launch
-//   2  MBCONV_IMAGE   smirk_mbconv_image_supported (stride 1: 14 x 14 halo tiles or whole images per workgroup), unless $SMIRK_DISABLE_MBCONV_IMAGE, and unless
+//   2  MBCONV_IMAGE   smirk_mbconv_image_supported (stride 1: one wave per 2 x 14 halo band, or whole images per workgroup), unless $SMIRK_DISABLE_MBCONV_IMAGE, and unless
 //                     $SMIRK_DISABLE_MBCONV_TILE keeps a block that row 4 also serves on the 8 x 8-tile kernel
 //   3  MBCONV_S2      stride 2, no residual, smirk_mbconv_s2_supported: one wave per output tile
 //   4  MBCONV_TILE    smirk_mbconv_supported: 8 x 8 output tiles.  The FALLBACK of rows 2 and 3 — feature maps of more than 224 pixels with a side that is no multiple of 14, and the
