@@ -209,7 +209,8 @@ int smirk_conv_igemm_f16x3(const SmirkConvDesc* d, const void* in0, const void* 
                            const float* scale, const float* shift, const void* residual, void* out, void* stream);
 /* The 16-bit class BASELINE config 5 trains in (the reference: torch.autocast(bfloat16) around smirk_trainer.py:184-332): same operands, descriptor and
  * output format, ONE fp16 MFMA per product block (the hi halves only, fp32 accumulation).  Used by the train-mode autograd functions when a module's
- * `train_arith` is "f16x1"; inference never calls it. */
+ * `train_arith` is "f16x1".  The whole-network generator entries reach the same arithmetic per level when SmirkGeneratorWeights.precision is
+ * SMIRK_PRECISION_F16X1 (smirk_generator_arith.h); they do not go through this entry's choices, which stay what the training path was measured with. */
 int smirk_conv_igemm_f16x1(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w,
                            const float* scale, const float* shift, const void* residual, void* out, void* stream);
 /* The generator's tail in ONE launch (smirk_generator.py:104-113 dec1conv2+norm2+relu2, :47-49,76 conv + sigmoid): 3x3 conv (zero pad 1, stride 1,
@@ -362,13 +363,14 @@ typedef struct SmirkConvLayer {
 } SmirkConvLayer;
 
 #define SMIRK_GEN_MAX_RES 16
-enum { SMIRK_PRECISION_F32 = 0, SMIRK_PRECISION_F16X3 = 1 };
+enum { SMIRK_PRECISION_F32 = 0, SMIRK_PRECISION_F16X3 = 1, SMIRK_PRECISION_F16X1 = 2 };
 
 /* SmirkGenerator(in_channels, out_channels, init_features, res_blocks) — src/smirk_generator.py:8-49 (parameter inventory), :51-86 (forward). */
 typedef struct SmirkGeneratorWeights {
     int32_t in_channels, out_channels, features, res_blocks;
-    int32_t precision;   /* SMIRK_PRECISION_*                                                                                  */
-    int32_t cin_pad;     /* channels of the packed network input (8 in f16x3 mode; in_channels rounded up to 4 in f32 mode)    */
+    int32_t precision;   /* SMIRK_PRECISION_*.  F16X1 (generator entries only, inference): split16 storage like F16X3, one fp16 MFMA per product block on
+                          * the levels smirk_generator_arith names (smirk_generator_arith.h), the three-MFMA product on the others                      */
+    int32_t cin_pad;     /* channels of the packed network input (8 in f16x3 / f16x1 mode; in_channels rounded up to 4 in f32 mode) */
     SmirkConvLayer enc[5][2];                  /* encoder1..4, bottleneck: conv1+norm1, conv2+norm2        (:13-27, _block :88-119) */
     SmirkConvLayer res[SMIRK_GEN_MAX_RES][2];  /* resnet_blocks[k].conv_block.{1,2} and .{5,6}            (:29-32, :121-178)       */
     SmirkConvLayer up[4];                      /* upconv4, 3, 2, 1: w = [(dy,dx,co)][ci], shift = bias     (:34-45)                 */

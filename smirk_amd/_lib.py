@@ -44,7 +44,7 @@ class SmirkConvLayer(C.Structure):
 
 
 GEN_MAX_RES, BACKBONE_MAX_BLOCKS = 16, 24
-PRECISION_F32, PRECISION_F16X3 = 0, 1
+PRECISION_F32, PRECISION_F16X3, PRECISION_F16X1 = 0, 1, 2             # F16X1: the generator's whole-network entries only (include/smirk_generator_arith.h)
 BACKBONE_FAMILIES = ("HEAD_FUSED", "CONV1X1", "MBCONV_IMAGE", "MBCONV_S2", "MBCONV_TILE", "DS_UNFUSED", "IR_UNFUSED")   # enum SmirkBackboneFamily, by code
 
 
@@ -303,6 +303,16 @@ GENPLAN_SIGS = {
 }
 GENPLAN_EXPORTS = tuple(GENPLAN_SIGS)
 
+# The extension table of include/smirk_generator_arith.h (which arithmetic every level of the generator runs in under the weights' precision, answered by the
+# function the forward asks; for tests and tools): the same shared object, a version of its own.
+GENARITH_ABI_VERSION = 1
+GEN_ARITH = ("F32", "F16X3", "F16X1")                                  # SMIRK_PRECISION_*, by code
+GENARITH_SIGS = {
+    "smirk_genarith_abi_version": (_i, []),
+    "smirk_generator_arith": (_i, [C.POINTER(SmirkGeneratorWeights), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+}
+GENARITH_EXPORTS = tuple(GENARITH_SIGS)
+
 _LIB = None
 
 
@@ -318,13 +328,13 @@ def lib():
             raise SmirkHipError(f"{LIB_PATH} not found: build it with `python -m smirk_amd.build` "
                                 "(smirk_amd has no CPU / eager fallback)")
         L = C.CDLL(LIB_PATH)
-        for table in (_SIGS, MICA_SIGS, EMOTION_SIGS, OPTIM_SIGS, HANDOFF_SIGS, GENPLAN_SIGS):
+        for table in (_SIGS, MICA_SIGS, EMOTION_SIGS, OPTIM_SIGS, HANDOFF_SIGS, GENPLAN_SIGS, GENARITH_SIGS):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)       # AttributeError => header / library mismatch
                 fn.restype, fn.argtypes = res, args
         if L.smirk_abi_version() != ABI_VERSION or L.smirk_mica_abi_version() != MICA_ABI_VERSION or L.smirk_emotion_abi_version() != EMOTION_ABI_VERSION or \
                 L.smirk_optim_abi_version() != OPTIM_ABI_VERSION or L.smirk_handoff_abi_version() != HANDOFF_ABI_VERSION or \
-                L.smirk_genplan_abi_version() != GENPLAN_ABI_VERSION:
+                L.smirk_genplan_abi_version() != GENPLAN_ABI_VERSION or L.smirk_genarith_abi_version() != GENARITH_ABI_VERSION:
             raise SmirkHipError("libsmirk_hip.so ABI version mismatch; rebuild")
         _LIB = L
     return _LIB

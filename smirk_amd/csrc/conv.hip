@@ -701,7 +701,8 @@ static int conv_for_batch_chunks(const SmirkConvDesc* d, int bc, Launch launch) 
 static const float* chunk_ptr(const void* p, size_t off) { return p ? (const float*)p + off : nullptr; }
 
 static int conv_dispatch_one(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale,
-                             const float* shift, const void* residual, void* out, void* stream, bool split, bool x1, float* stats, int* stats_rows) {
+                             const float* shift, const void* residual, void* out, void* stream, bool split, bool x1, float* stats, int* stats_rows,
+                             bool gen_x1 = false) {
     if (!d || !in0 || !w || !out) return SMIRK_ERR_BAD_ARG;
     if (stats_rows) *stats_rows = 0;
     if (x1 && !split) return SMIRK_ERR_BAD_ARG;
@@ -738,8 +739,11 @@ static int conv_dispatch_one(const SmirkConvDesc* d, const void* in0, const void
     hipStream_t st = (hipStream_t)stream;
 
     // Kernel family, first match wins: ring -> patch -> halo -> ping-pong -> implicit GEMM.  Every family reads its own switch, once per launch.
-    // F16X1 lives in conv_igemm_kernel and conv_halo_x1_kernel only: the other specialised kernels issue the three-MFMA product unconditionally.
+    // F16X1 lives in conv_igemm_kernel and conv_halo_x1_kernel, and — for the generator's inference plan alone (gen_x1: smirk_conv_dispatch_gen_x1) — in the
+    // 64-channel ring kernel: the other specialised kernels issue the three-MFMA product unconditionally.
     const bool f16x3 = split && !x1;
+    if (gen_x1 && x1 && !smirk_switch(SMIRK_SW_DISABLE_PATCH_KERNEL) && smirk_conv3x3_ring64_x1_eligible(d, residual != nullptr))
+        return smirk_conv3x3_ring64_launch(d, in0, in1, w, scale, shift, out, nullptr, st, nullptr, nullptr, true);
     const bool patch_ok = !smirk_switch(SMIRK_SW_DISABLE_PATCH_KERNEL) && f16x3;         // A/B switch: neither the patch nor the ring kernels
     if (patch_ok && smirk_conv3x3_ring64_eligible(d, residual != nullptr))               // the 64-output-channel layers on large images
         return smirk_conv3x3_ring64_launch(d, in0, in1, w, scale, shift, out, nullptr, st, stats, stats_rows);      // (writes statistics, and its row count, only for a raw epilogue)
@@ -762,15 +766,20 @@ static int conv_dispatch_one(const SmirkConvDesc* d, const void* in0, const void
 
 static int conv_dispatch(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale,
                          const float* shift, const void* residual, void* out, void* stream, bool split, bool x1 = false, float* stats = nullptr,
-                         int* stats_rows = nullptr) {
+                         int* stats_rows = nullptr, bool gen_x1 = false) {
     if (!d || !in0 || !w || !out) return SMIRK_ERR_BAD_ARG;
     if (stats_rows) *stats_rows = 0;                            // (a layer run as several batch chunks writes no statistics: the caller reduces the stored tensor)
     const int bc = (d->B > 0 && d->H > 0 && d->W > 0 && d->C0 > 0 && d->C1 >= 0) ? conv_batch_chunk(d, split) : d->B;
-    if (bc >= d->B) return conv_dispatch_one(d, in0, in1, w, scale, shift, residual, out, stream, split, x1, stats, stats_rows);
+    if (bc >= d->B) return conv_dispatch_one(d, in0, in1, w, scale, shift, residual, out, stream, split, x1, stats, stats_rows, gen_x1);
     return conv_for_batch_chunks(d, bc, [&](const ConvChunk& c) {
         return conv_dispatch_one(&c.d, (const float*)in0 + c.in0, chunk_ptr(in1, c.in1), w, scale, shift, chunk_ptr(residual, c.out), (float*)out + c.out, stream,
-                                 split, x1, nullptr, nullptr);
+                                 split, x1, nullptr, nullptr, gen_x1);
     });
+}
+
+int smirk_conv_dispatch_gen_x1(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale, const float* shift, const void* residual,
+                               void* out, void* stream) {
+    return conv_dispatch(d, in0, in1, w, scale, shift, residual, out, stream, true, true, nullptr, nullptr, true);
 }
 
 extern "C" int smirk_conv_igemm_f32(const SmirkConvDesc* d, const float* in0, const float* in1, const float* w,
@@ -797,8 +806,8 @@ bool smirk_conv3x3_tail_supported(const SmirkConvDesc* d, int fcout) {
     return d && fcout > 0 && fcout <= 4 && d->Cout == 32 && d->act == SMIRK_ACT_RELU && smirk_conv3x3_patch_eligible(d, false);
 }
 
-extern "C" int smirk_conv3x3_pool_f16x3(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale, const float* shift, void* out,
-                                        void* pooled, void* stream) {
+int smirk_conv3x3_pool_launch(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale, const float* shift, void* out,
+                              void* pooled, void* stream, bool x1) {
     if (!d || !in0 || !w || !out || !pooled) return SMIRK_ERR_BAD_ARG;
     if (d->C0 % 8 || d->C1 % 8 || (d->C1 > 0 && !in1) || d->H % 2 || d->W % 2) return SMIRK_ERR_BAD_ARG;
     if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->C0 <= 0) return SMIRK_ERR_BAD_ARG;
@@ -806,8 +815,13 @@ extern "C" int smirk_conv3x3_pool_f16x3(const SmirkConvDesc* d, const void* in0,
     const int bc = conv_batch_chunk(d, true);
     return conv_for_batch_chunks(d, bc, [&](const ConvChunk& c) {       // (same-size output, H and W even: the pooled tensor is a quarter of it)
         return smirk_conv3x3_ring64_launch(&c.d, (const float*)in0 + c.in0, chunk_ptr(in1, c.in1), w, scale, shift, (float*)out + c.out, (float*)pooled + c.out / 4,
-                                           (hipStream_t)stream);
+                                           (hipStream_t)stream, nullptr, nullptr, x1);
     });
+}
+
+extern "C" int smirk_conv3x3_pool_f16x3(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale, const float* shift, void* out,
+                                        void* pooled, void* stream) {
+    return smirk_conv3x3_pool_launch(d, in0, in1, w, scale, shift, out, pooled, stream, false);
 }
 
 extern "C" int smirk_conv3x3_tail_f16x3(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale,
@@ -832,7 +846,8 @@ extern "C" int smirk_conv_igemm_f16x3(const SmirkConvDesc* d, const void* in0, c
 
 // The same convolution on the same split16 operands with ONE MFMA per product block: only the hi halves (fp16(x), 11 significand bits) enter the product,
 // accumulation stays fp32.  This is the 16-bit class of BASELINE config 5 (the reference trains under bf16 autocast: 8 significand bits); the output is
-// written split16 like every activation, so it feeds either mode.  Always conv_igemm_kernel (the three-MFMA product is compiled into the specialised kernels).
+// written split16 like every activation, so it feeds either mode.  conv_halo_x1_kernel where the halo family serves the shape, conv_igemm_kernel<..., X1> otherwise:
+// what the training path was measured with (tests/test_conv_dispatch_gpu.py).  The generator's f16x1 inference plan comes in through smirk_conv_dispatch_gen_x1 above.
 extern "C" int smirk_conv_igemm_f16x1(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w,
                                       const float* scale, const float* shift, const void* residual, void* out,
                                       void* stream) {

@@ -126,14 +126,21 @@ static inline void conv_prof_next(const char* name, const ConvArgs& a) {
 // conv_ring.hip: 16 x 16 patches, weights streamed through an LDS ring, two workgroups per CU (Cout = 64 at 112 x 112), optional fused 2 x 2 max-pool
 bool smirk_conv3x3_ring64_eligible(const SmirkConvDesc* d, bool has_residual);
 int smirk_conv3x3_ring64_launch(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale, const float* shift, void* out,
-                                void* pooled, hipStream_t st, float* stats = nullptr, int* stats_rows = nullptr);
+                                void* pooled, hipStream_t st, float* stats = nullptr, int* stats_rows = nullptr, bool x1 = false);
+bool smirk_conv3x3_ring64_x1_eligible(const SmirkConvDesc* d, bool has_residual);      // x1: the one-MFMA form (the generator's f16x1 inference arithmetic), Cout = 64 only
 // conv_upcat.hip: a decoder level's ConvTranspose2d(2c -> c, k2 s2) composed into the 3x3 convolution over cat(up, skip) (c = 32 / 64, split-fp16 only); the
 // composed weights and the 16 shift rows are rebuilt per call into caller-provided workspace
 bool smirk_conv3x3_upcat_eligible(int c, int H, int W);
 size_t smirk_conv3x3_upcat_weff_bytes(int c);
 size_t smirk_conv3x3_upcat_shift_bytes(int c);
 int smirk_conv3x3_upcat_launch(int c, const void* d, const void* e, const SmirkConvLayer* up, const SmirkConvLayer* conv, void* out, int B, int H, int W,
-                               void* weff, void* shift4, hipStream_t st);
+                               void* weff, void* shift4, hipStream_t st, bool x1 = false);      // x1: c = 64 only
+// conv.hip, for the generator's plan alone (network.hip): the dispatcher in the f16x1 inference arithmetic, where a layer may also take the one-MFMA ring kernel
+// (the public smirk_conv_igemm_f16x1 keeps choosing what the training path was measured with), and the pool-fused entry in either arithmetic
+int smirk_conv_dispatch_gen_x1(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale, const float* shift, const void* residual,
+                               void* out, void* stream);
+int smirk_conv3x3_pool_launch(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale, const float* shift, void* out,
+                              void* pooled, void* stream, bool x1);
 // conv_patch.hip: persistent halo-patch kernel for the large-image / few-channel 3x3 layers (split-fp16 only)
 bool smirk_conv3x3_patch_eligible(const SmirkConvDesc* d, bool has_residual);
 int smirk_conv3x3_patch_launch(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale,
@@ -161,7 +168,7 @@ size_t smirk_updeep_shift_bytes(int c);
 size_t smirk_updeep_wskip_bytes(int c);
 bool smirk_updeep_eligible(int B, int H, int W, int c);                 // H x W: the FINE image; both launches pass smirk_conv_halo_eligible with their own M
 int smirk_updeep_compose(const SmirkUpdeepLevel* lv, int nlv, hipStream_t st);
-int smirk_updeep_coarse_launch(const SmirkUpdeepLevel* lv, const void* d, void* partial, int B, int H, int W, hipStream_t st);
+int smirk_updeep_coarse_launch(const SmirkUpdeepLevel* lv, const void* d, void* partial, int B, int H, int W, bool x1, hipStream_t st);   // x1: conv_halo_up_x1_kernel
 // conv_pp.hip: 8-wave ping-pong kernel (256 x 128 tile, 3-stage ring) for the deep split-fp16 3x3 layers
 bool smirk_conv_pp_eligible(const ConvArgs& a);
 int smirk_conv_pp_launch(const ConvArgs& a, hipStream_t st);

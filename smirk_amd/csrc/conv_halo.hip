@@ -410,6 +410,9 @@ __global__ __launch_bounds__(512, 2) void conv_halo_x1_stats_kernel(ConvArgs a) 
 // the coarse half of a composed decoder level (UP above): grid = 4 classes x tiles, a.d describes the COARSE tensor, a.w = Weff, a.shift = the 16 shift rows
 template <int NPA>
 __global__ __launch_bounds__(512, 2) void conv_halo_up_kernel(ConvArgs a) { conv_halo_body<NPA, 0, false, false, true>(a); }
+// ... in the generator's f16x1 inference arithmetic: the same walk over the same composed pairs, one MFMA per product block on their hi halves (X1 above)
+template <int NPA>
+__global__ __launch_bounds__(512, 2) void conv_halo_up_x1_kernel(ConvArgs a) { conv_halo_body<NPA, 0, true, false, true>(a); }
 
 // Serves: split-fp16, 3x3, stride 1, pad 1, NHWC out, both sources power-of-two multiples of 32 channels, N a multiple of 128, W <= 63, operands < 2 GiB.
 bool smirk_conv_halo_eligible(const ConvArgs& a) {
@@ -636,18 +639,19 @@ int smirk_updeep_compose(const SmirkUpdeepLevel* lv, int nlv, hipStream_t st) {
 }
 
 // launch 1: partial'[B][H][W][c] from the coarse tensor d[B][H/2][W/2][2c]
-int smirk_updeep_coarse_launch(const SmirkUpdeepLevel* lv, const void* d, void* partial, int B, int H, int W, hipStream_t st) {
+int smirk_updeep_coarse_launch(const SmirkUpdeepLevel* lv, const void* d, void* partial, int B, int H, int W, bool x1, hipStream_t st) {
     if (!lv || !d || !partial || !smirk_updeep_eligible(B, H, W, lv->c)) return SMIRK_ERR_UNSUPPORTED;
     ConvArgs a = updeep_args(B, H / 2, W / 2, 2 * lv->c, lv->c, 4);
     a.in0 = (const float*)d; a.w = (const float*)lv->weff; a.scale = lv->conv->scale; a.shift = (const float*)lv->shift16; a.out = (float*)partial;
     constexpr size_t lds = 4 * HS_BN * 128 + 2 * (5 * 8 * 1024 + 128);        // four ring stages + two 5-piece halo buffers (256 + W + 1 <= 320 rows for W <= 63)
-    if (const int rc = smirk_raise_dynamic_lds((const void*)conv_halo_up_kernel<5>, 160 * 1024)) return rc;
+    if (const int rc = smirk_raise_dynamic_lds(x1 ? (const void*)conv_halo_up_x1_kernel<5> : (const void*)conv_halo_up_kernel<5>, 160 * 1024)) return rc;
     const int ntm = (a.M + HS_BM - 1) / HS_BM, ntn = a.N / HS_BN;
     if (g_smirk_prof_on) {
         const double px = (double)a.M;
-        smirk_prof_next("conv_halo_up_kernel<5>[256x128,8w,halo,composed upconv]", 2.0 * (4.0 * a.M) * a.N * a.K,
-                        4.0 * (px * a.Cin + 4.0 * px * a.N + 4.0 * a.N * a.K));
+        smirk_prof_next(x1 ? "conv_halo_up_x1_kernel<5>[256x128,8w,halo,composed upconv,f16x1]" : "conv_halo_up_kernel<5>[256x128,8w,halo,composed upconv]",
+                        2.0 * (4.0 * a.M) * a.N * a.K, 4.0 * (px * a.Cin + 4.0 * px * a.N + 4.0 * a.N * a.K));
     }
-    SMIRK_LAUNCH((conv_halo_up_kernel<5>), dim3(4 * ntm * ntn), dim3(512), lds, st, a);
+    if (x1) SMIRK_LAUNCH((conv_halo_up_x1_kernel<5>), dim3(4 * ntm * ntn), dim3(512), lds, st, a);
+    else SMIRK_LAUNCH((conv_halo_up_kernel<5>), dim3(4 * ntm * ntn), dim3(512), lds, st, a);
     return smirk_launch_status();
 }

@@ -47,7 +47,9 @@ __device__ __forceinline__ void rg_frag_ready(const half8& a, const half8& b, co
 }
 
 // TN = output channels / 32 (1: the two-source 64 -> 32 layer at 224 x 224, 2: the 64-channel layers at 112 x 112); POOL: also write the 2 x 2 max-pool of the output
-template <int TN, bool POOL, bool STATS = false>
+// X1: one fp16 MFMA per product block on the hi halves (the generator's "f16x1" inference arithmetic, conv_halo.hip): no lo fragment is read from LDS, one MFMA group
+//     of the three remains, the epilogue takes acc0 alone.  The DMA schedule (and so every counted wait) is the x3 one: the lo halves travel with their pixels.
+template <int TN, bool POOL, bool STATS = false, bool X1 = false>
 __global__ __launch_bounds__(256, TN == 1 ? 3 : 2) void conv3x3_ring_kernel(RingArgs a) {
     constexpr int COUT = 32 * TN, STAGE = COUT * 128, EPI_LD = COUT + 4, GPR = COUT / 8, ITEMS = 32 * GPR / 64;
     extern __shared__ __attribute__((aligned(16))) char rg_lds[];
@@ -158,12 +160,12 @@ __global__ __launch_bounds__(256, TN == 1 ? 3 : 2) void conv3x3_ring_kernel(Ring
                     for (int i = 0; i < 2; ++i) {
                         const unsigned disp = (unsigned)((2 * i + KY) * RG_PH * 128);
                         ah[s][i] = *(const half8*)(rg_lds + ((av ^ ch) + disp));
-                        al[s][i] = *(const half8*)(rg_lds + ((av ^ cl) + disp));
+                        if constexpr (!X1) al[s][i] = *(const half8*)(rg_lds + ((av ^ cl) + disp));
                     }
 #pragma unroll
                     for (int j = 0; j < TN; ++j) {
                         bh[s][j] = *(const half8*)(rg_lds + ((bv ^ ch) + (unsigned)(ST * STAGE + j * 4096)));
-                        bl[s][j] = *(const half8*)(rg_lds + ((bv ^ cl) + (unsigned)(ST * STAGE + j * 4096)));
+                        if constexpr (!X1) bl[s][j] = *(const half8*)(rg_lds + ((bv ^ cl) + (unsigned)(ST * STAGE + j * 4096)));
                     }
                 }
                 // matrix section at priority 1 (the other resident workgroup's loads / address arithmetic yield the issue slots): +0.5-3 % on the 64-channel
@@ -171,20 +173,23 @@ __global__ __launch_bounds__(256, TN == 1 ? 3 : 2) void conv3x3_ring_kernel(Ring
                 if constexpr (TN == 2) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
-                    rg_frag_ready(ah[s][1], al[s][1], bh[s][TN - 1], bl[s][TN - 1]);
+                    if constexpr (X1) rg_frag_ready(ah[s][0], ah[s][1], bh[s][0], bh[s][TN - 1]);
+                    else rg_frag_ready(ah[s][1], al[s][1], bh[s][TN - 1], bl[s][TN - 1]);
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int i = 0; i < 2; ++i)
 #pragma unroll
                         for (int j = 0; j < TN; ++j) acc0[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s][i], bh[s][j], (FIRST && s == 0) ? z16 : acc0[i][j], 0, 0, 0);
+                    if constexpr (!X1) {
 #pragma unroll
-                    for (int i = 0; i < 2; ++i)
+                        for (int i = 0; i < 2; ++i)
 #pragma unroll
-                        for (int j = 0; j < TN; ++j) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s][i], bl[s][j], (FIRST && s == 0) ? z16 : acc1[i][j], 0, 0, 0);
+                            for (int j = 0; j < TN; ++j) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s][i], bl[s][j], (FIRST && s == 0) ? z16 : acc1[i][j], 0, 0, 0);
 #pragma unroll
-                    for (int i = 0; i < 2; ++i)
+                        for (int i = 0; i < 2; ++i)
 #pragma unroll
-                        for (int j = 0; j < TN; ++j) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[s][i], bh[s][j], acc1[i][j], 0, 0, 0);
+                            for (int j = 0; j < TN; ++j) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[s][i], bh[s][j], acc1[i][j], 0, 0, 0);
+                    }
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 if constexpr (TN == 2) __builtin_amdgcn_s_setprio(0);
@@ -210,7 +215,7 @@ __global__ __launch_bounds__(256, TN == 1 ? 3 : 2) void conv3x3_ring_kernel(Ring
                 float x16[16];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    x16[r] = acc0[i][j][r] + acc1[i][j][r] * (1.0f / 2048.0f);
+                    x16[r] = X1 ? acc0[i][j][r] : acc0[i][j][r] + acc1[i][j][r] * (1.0f / 2048.0f);
                     ebuf[mfma32_row(r, lane) * EPI_LD + j * 32 + fr] = x16[r];
                 }
                 if constexpr (STATS) stats_block(x16, lane, 32, pt1[j], pt2[j]);
@@ -290,16 +295,19 @@ bool smirk_conv3x3_ring64_eligible(const SmirkConvDesc* d, bool has_residual) {
     if ((d->Cout != 64 && !(d->Cout == 32 && d->C0 + d->C1 >= 64)) || d->C0 < 32 || d->C0 % 32 || d->C1 % 32 || (d->C0 & (d->C0 - 1)) || (d->C1 & (d->C1 - 1))) return false;
     return conv_inputs_fit32(*d);                                     // (the weights, 9 (C0 + C1) x 64 at most, cannot reach the limit before an input does)
 }
+// ... and of those, what the one-MFMA instantiations serve: the 64-output-channel layers
+bool smirk_conv3x3_ring64_x1_eligible(const SmirkConvDesc* d, bool has_residual) { return d->Cout == 64 && smirk_conv3x3_ring64_eligible(d, has_residual); }
 
-template <int TN, bool POOL, bool STATS = false>
+template <int TN, bool POOL, bool STATS = false, bool X1 = false>
 static int rg_launch(const RingArgs& a, int grid, hipStream_t st) {
-    if (const int rc = smirk_raise_dynamic_lds((const void*)conv3x3_ring_kernel<TN, POOL, STATS>, RG_LDS_BYTES(32 * TN))) return rc;
-    SMIRK_LAUNCH((conv3x3_ring_kernel<TN, POOL, STATS>), dim3(grid), dim3(256), RG_LDS_BYTES(32 * TN), st, a);
+    if (const int rc = smirk_raise_dynamic_lds((const void*)conv3x3_ring_kernel<TN, POOL, STATS, X1>, RG_LDS_BYTES(32 * TN))) return rc;
+    SMIRK_LAUNCH((conv3x3_ring_kernel<TN, POOL, STATS, X1>), dim3(grid), dim3(256), RG_LDS_BYTES(32 * TN), st, a);
     return smirk_launch_status();
 }
 
 int smirk_conv3x3_ring64_launch(const SmirkConvDesc* d, const void* in0, const void* in1, const void* w, const float* scale, const float* shift, void* out,
-                                void* pooled, hipStream_t st, float* stats, int* stats_rows) {
+                                void* pooled, hipStream_t st, float* stats, int* stats_rows, bool x1) {
+    if (x1 && (d->Cout != 64 || stats)) return SMIRK_ERR_UNSUPPORTED;  // the one-MFMA form exists for the 64-channel inference layers only (smirk_conv3x3_ring64_x1_eligible)
     RingArgs a;
     a.in0 = (const float*)in0; a.in1 = (const float*)in1; a.w = (const float*)w; a.scale = scale; a.shift = shift;
     a.out = (float*)out; a.pool = (float*)pooled;
@@ -313,9 +321,11 @@ int smirk_conv3x3_ring64_launch(const SmirkConvDesc* d, const void* in0, const v
     if (stats && stats_rows && !pooled && !scale && !shift && d->act == SMIRK_ACT_NONE) { a.stats = stats; *stats_rows = grid * 4; }   // train mode: raw output + its column sums
     if (g_smirk_prof_on) {
         const double px = (double)d->B * d->H * d->W, K = 9.0 * (d->C0 + d->C1);
-        smirk_prof_next(d->Cout == 32 ? "conv3x3_ring_kernel<1>[16x16 patch,ring]" : pooled ? "conv3x3_ring_kernel<2,pool>[16x16 patch,ring]" : "conv3x3_ring_kernel<2>[16x16 patch,ring]",
+        smirk_prof_next(x1 ? (pooled ? "conv3x3_ring_kernel<2,pool>[16x16 patch,ring,f16x1]" : "conv3x3_ring_kernel<2>[16x16 patch,ring,f16x1]")
+                        : d->Cout == 32 ? "conv3x3_ring_kernel<1>[16x16 patch,ring]" : pooled ? "conv3x3_ring_kernel<2,pool>[16x16 patch,ring]" : "conv3x3_ring_kernel<2>[16x16 patch,ring]",
                         2.0 * px * d->Cout * K, px * (d->C0 + d->C1) * 4.0 + px * d->Cout * 4.0 * (pooled ? 1.25 : 1.0) + K * d->Cout * 4.0);
     }
+    if (x1) return pooled ? rg_launch<2, true, false, true>(a, grid, st) : rg_launch<2, false, false, true>(a, grid, st);
     if (a.stats) return d->Cout == 32 ? rg_launch<1, false, true>(a, grid, st) : rg_launch<2, false, true>(a, grid, st);
     if (d->Cout == 32) return pooled ? SMIRK_ERR_UNSUPPORTED : rg_launch<1, false>(a, grid, st);
     return pooled ? rg_launch<2, true>(a, grid, st) : rg_launch<2, false>(a, grid, st);

@@ -111,7 +111,9 @@ __global__ __launch_bounds__(256) void upcat_compose_kernel(const float* wup, co
 }
 
 // TN = output channels / 32 (1: decoder level 1, 64 @ 112^2 + 32 @ 224^2 -> 32; 2: level 2, 128 @ 56^2 + 64 @ 112^2 -> 64)
-template <int TN>
+// X1: one fp16 MFMA per product block on the hi halves (the generator's "f16x1" inference arithmetic, as in conv_ring.hip): no lo fragment is read from LDS or — the
+//     composed half — from global, one MFMA group of the three remains, the epilogue takes acc0 alone; the DMA schedule and its counted waits are the x3 ones.
+template <int TN, bool X1 = false>
 __global__ __launch_bounds__(256, TN == 1 ? 3 : 2) void conv3x3_upcat_kernel(UpcatArgs a) {
     constexpr int COUT = 32 * TN, C = COUT, CIN = 2 * C, K = 9 * CIN, STAGE = COUT * 128, EPI_LD = COUT + 4, GPR = COUT / 8, ITEMS = 32 * GPR / 64;
     constexpr int NSK = TN, NCC = 2 * TN, RING = 3 * STAGE;
@@ -216,14 +218,20 @@ __global__ __launch_bounds__(256, TN == 1 ? 3 : 2) void conv3x3_upcat_kernel(Upc
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int j = 0; j < TN; ++j) acc0[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], zero ? z16 : acc0[i][j], 0, 0, 0);
+            if constexpr (!X1) {
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
+                for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], zero ? z16 : acc1[i][j], 0, 0, 0);
+                    for (int j = 0; j < TN; ++j) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], zero ? z16 : acc1[i][j], 0, 0, 0);
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
+                for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc1[i][j], 0, 0, 0);
+                    for (int j = 0; j < TN; ++j) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc1[i][j], 0, 0, 0);
+            }
+        };
+        auto frag_ready = [&](const half8 (&ah)[2], const half8 (&al)[2], const half8 (&bh)[TN], const half8 (&bl)[TN]) {
+            if constexpr (X1) uc_frag_ready(ah[0], ah[1], bh[0], bh[TN - 1]);
+            else uc_frag_ready(ah[1], al[1], bh[TN - 1], bl[TN - 1]);
         };
         auto load_a = [&](unsigned av, unsigned tile_disp, half8 (&ah)[2][2], half8 (&al)[2][2]) {
 #pragma unroll
@@ -232,7 +240,7 @@ __global__ __launch_bounds__(256, TN == 1 ? 3 : 2) void conv3x3_upcat_kernel(Upc
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     ah[s][i] = *(const half8*)(uc_lds + ((av ^ ch) + i * tile_disp));
-                    al[s][i] = *(const half8*)(uc_lds + ((av ^ cl) + i * tile_disp));
+                    if constexpr (!X1) al[s][i] = *(const half8*)(uc_lds + ((av ^ cl) + i * tile_disp));
                 }
             }
         };
@@ -266,13 +274,13 @@ __global__ __launch_bounds__(256, TN == 1 ? 3 : 2) void conv3x3_upcat_kernel(Upc
 #pragma unroll
                     for (int j = 0; j < TN; ++j) {
                         bh[s][j] = *(const half8*)(uc_lds + ((bv ^ ch) + (unsigned)(ST * STAGE + j * 4096)));
-                        bl[s][j] = *(const half8*)(uc_lds + ((bv ^ cl) + (unsigned)(ST * STAGE + j * 4096)));
+                        if constexpr (!X1) bl[s][j] = *(const half8*)(uc_lds + ((bv ^ cl) + (unsigned)(ST * STAGE + j * 4096)));
                     }
                 }
                 if constexpr (TN == 2) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
-                    uc_frag_ready(ah[s][1], al[s][1], bh[s][TN - 1], bl[s][TN - 1]);
+                    frag_ready(ah[s], al[s], bh[s], bl[s]);
                     __builtin_amdgcn_sched_barrier(0);
                     mfma_step(ah[s], al[s], bh[s], bl[s], FIRST && s == 0);
                     __builtin_amdgcn_sched_barrier(0);
@@ -294,7 +302,7 @@ __global__ __launch_bounds__(256, TN == 1 ? 3 : 2) void conv3x3_upcat_kernel(Upc
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 bh[s][j] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rsF, fL, so + j * 4096, 0));
-                bl[s][j] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rsF, fL, so + j * 4096 + 1024, 0));
+                if constexpr (!X1) bl[s][j] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rsF, fL, so + j * 4096 + 1024, 0));
             }
         };
         for (int pr = 0; pr < NCC / 2; ++pr) {
@@ -315,7 +323,7 @@ __global__ __launch_bounds__(256, TN == 1 ? 3 : 2) void conv3x3_upcat_kernel(Upc
                 if constexpr (TN == 2) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
-                    uc_frag_ready(ah[s][1], al[s][1], bh[s][TN - 1], bl[s][TN - 1]);
+                    frag_ready(ah[s], al[s], bh[s], bl[s]);
                     __builtin_amdgcn_sched_barrier(0);
                     mfma_step(ah[s], al[s], bh[s], bl[s], false);
                     __builtin_amdgcn_sched_barrier(0);
@@ -339,7 +347,7 @@ __global__ __launch_bounds__(256, TN == 1 ? 3 : 2) void conv3x3_upcat_kernel(Upc
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) ebuf[mfma32_row(r, lane) * EPI_LD + j * 32 + fr] = acc0[i][j][r] + acc1[i][j][r] * (1.0f / 2048.0f);
+                for (int r = 0; r < 16; ++r) ebuf[mfma32_row(r, lane) * EPI_LD + j * 32 + fr] = X1 ? acc0[i][j][r] : acc0[i][j][r] + acc1[i][j][r] * (1.0f / 2048.0f);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // per-wave transpose buffer: LDS operations of one wave execute in order
 #pragma unroll
@@ -388,14 +396,14 @@ bool smirk_conv3x3_upcat_eligible(int c, int H, int W) {
 size_t smirk_conv3x3_upcat_weff_bytes(int c) { return (size_t)32 * c * c * 4; }       // 4 classes x 4 taps x 2c x c split-fp16 pairs
 size_t smirk_conv3x3_upcat_shift_bytes(int c) { return (size_t)16 * c * 4; }
 
-template <int TN>
+template <int TN, bool X1 = false>
 static int uc_run(const UpcatArgs& proto, const float* wup, const float* bup, const float* shift, float* weff, float* shift4, int B, hipStream_t st) {
     constexpr int C = 32 * TN, PER_CU = TN == 1 ? 3 : 2;
     constexpr int NTHREADS = 4 * (2 * TN) * 4 * TN * 2 * 64 + 16 * C;
     if (g_smirk_prof_on) smirk_prof_next(TN == 1 ? "upcat_compose_kernel<1>" : "upcat_compose_kernel<2>", 2.0 * 4 * 9 * C * C * 2 * C, 4.0 * (4 * C * 2 * C + 18 * C * C + 32 * C * C));
     SMIRK_LAUNCH((upcat_compose_kernel<TN>), dim3((NTHREADS + 255) / 256), dim3(256), 0, st, wup, bup, proto.w3, proto.scale, shift, weff, shift4);
     if (const int rc = smirk_launch_status()) return rc;
-    if (const int rc = smirk_raise_dynamic_lds((const void*)conv3x3_upcat_kernel<TN>, UC_LDS_BYTES(C))) return rc;
+    if (const int rc = smirk_raise_dynamic_lds((const void*)conv3x3_upcat_kernel<TN, X1>, UC_LDS_BYTES(C))) return rc;
     // batch chunks whose skip / output tensors stay below 2 GiB (32-bit buffer offsets; the coarse tensor is half their size)
     const long long per_img = (long long)proto.H * proto.W * C * 4;
     int bc = (int)((CONV_BUF_LIMIT - 1) / per_img);
@@ -412,10 +420,11 @@ static int uc_run(const UpcatArgs& proto, const float* wup, const float* bup, co
         const int grid = a.npatch < PER_CU * n_cu ? a.npatch : PER_CU * n_cu;
         if (g_smirk_prof_on) {
             const double px = (double)nb * proto.H * proto.W;
-            smirk_prof_next(TN == 1 ? "conv3x3_upcat_kernel<1>[16x16 patch,composed upconv]" : "conv3x3_upcat_kernel<2>[16x16 patch,composed upconv]",
+            smirk_prof_next(X1 ? "conv3x3_upcat_kernel<2>[16x16 patch,composed upconv,f16x1]"
+                            : TN == 1 ? "conv3x3_upcat_kernel<1>[16x16 patch,composed upconv]" : "conv3x3_upcat_kernel<2>[16x16 patch,composed upconv]",
                             2.0 * px * C * (4.0 * 2 * C + 9.0 * C), px * 0.25 * 2 * C * 4.0 + 2.0 * px * C * 4.0 + (9.0 * C * C + 32.0 * C * C) * 4.0);
         }
-        SMIRK_LAUNCH((conv3x3_upcat_kernel<TN>), dim3(grid), dim3(256), UC_LDS_BYTES(C), st, a);
+        SMIRK_LAUNCH((conv3x3_upcat_kernel<TN, X1>), dim3(grid), dim3(256), UC_LDS_BYTES(C), st, a);
         if (const int rc = smirk_launch_status()) return rc;
     }
     return SMIRK_OK;
@@ -424,12 +433,13 @@ static int uc_run(const UpcatArgs& proto, const float* wup, const float* bup, co
 // d: coarse tensor [B][H/2][W/2][2c]; e: skip tensor [B][H][W][c]; up: the ConvTranspose2d layer (w = [(dy,dx,co)][ci], shift = bias); conv: the level's first
 // 3x3 layer over cat(up, e) with its folded BatchNorm; out [B][H][W][c] = ReLU(BN(conv)); weff / shift4: workspace of smirk_conv3x3_upcat_{weff,shift}_bytes(c)
 int smirk_conv3x3_upcat_launch(int c, const void* d, const void* e, const SmirkConvLayer* up, const SmirkConvLayer* conv, void* out, int B, int H, int W,
-                               void* weff, void* shift4, hipStream_t st) {
-    if (!smirk_conv3x3_upcat_eligible(c, H, W)) return SMIRK_ERR_UNSUPPORTED;
+                               void* weff, void* shift4, hipStream_t st, bool x1) {
+    if (!smirk_conv3x3_upcat_eligible(c, H, W) || (x1 && c != 64)) return SMIRK_ERR_UNSUPPORTED;   // (the one-MFMA form: the 64-channel level only)
     if (!d || !e || !out || !weff || !shift4 || !up->w || !up->shift || up->scale || !conv->w || !conv->scale || !conv->shift || B <= 0) return SMIRK_ERR_BAD_ARG;
     UpcatArgs a;
     a.d = (const float*)d; a.e = (const float*)e; a.w3 = (const float*)conv->w; a.weff = (const float*)weff; a.scale = conv->scale; a.shift4 = (const float*)shift4;
     a.out = (float*)out; a.B = B; a.H = H; a.W = W; a.npatch = 0;
+    if (x1) return uc_run<2, true>(a, (const float*)up->w, up->shift, conv->shift, (float*)weff, (float*)shift4, B, st);
     return c == 32 ? uc_run<1>(a, (const float*)up->w, up->shift, conv->shift, (float*)weff, (float*)shift4, B, st)
                    : uc_run<2>(a, (const float*)up->w, up->shift, conv->shift, (float*)weff, (float*)shift4, B, st);
 }

@@ -24,6 +24,7 @@
 #include "conv_common.h"
 #include "../../include/smirk_handoff.h"
 #include "../../include/smirk_generator_plan.h"
+#include "../../include/smirk_generator_arith.h"
 
 namespace {
 
@@ -50,9 +51,11 @@ struct Rot {
 
 inline size_t act_bytes(int B, int H, int W, int C) { return (size_t)B * H * W * C * 4; }
 
-int conv_call(bool split, const SmirkConvDesc& d, const void* in0, const void* in1, const SmirkConvLayer& L, const void* residual, void* out,
+// arith: the SMIRK_PRECISION_* value of the layer (the generator: gen_level_arith; the backbones: their weights' precision)
+int conv_call(int arith, const SmirkConvDesc& d, const void* in0, const void* in1, const SmirkConvLayer& L, const void* residual, void* out,
               void* stream) {
-    return split ? smirk_conv_igemm_f16x3(&d, in0, in1, L.w, L.scale, L.shift, residual, out, stream)
+    if (arith == SMIRK_PRECISION_F16X1) return smirk_conv_dispatch_gen_x1(&d, in0, in1, L.w, L.scale, L.shift, residual, out, stream);
+    return arith == SMIRK_PRECISION_F16X3 ? smirk_conv_igemm_f16x3(&d, in0, in1, L.w, L.scale, L.shift, residual, out, stream)
                  : smirk_conv_igemm_f32(&d, (const float*)in0, (const float*)in1, (const float*)L.w, L.scale, L.shift, (const float*)residual,
                                         (float*)out, stream);
 }
@@ -79,10 +82,29 @@ SmirkConvDesc desc1x1(int B, int H, int W, int cin, int cout, bool relu, bool co
         if (rc_ != SMIRK_OK) return rc_; \
     } while (0)
 
+// ---- the arithmetic of a level ------------------------------------------------------------------------------------------------------------------------------------
+// SMIRK_PRECISION_F16X1 (inference only) keeps the split16 storage of F16X3 everywhere — weight images, workspace, pack / pool / hand-off kernels, range
+// audit — and issues ONE fp16 MFMA per product block, on the hi halves, in every convolution of the levels l >= GEN_X1_FROM: both encoder convolutions, the
+// ConvTranspose2d or its composed form, both decoder convolutions, and (level 4) the bottleneck and the ResNet blocks.  Levels below run exactly the launches of F16X3.
+// A layer's arithmetic is a function of the precision and its level ALONE (never of the batch, the chains, taps or a kernel switch): where a kernel family has no
+// one-MFMA form (enc1_fused, the 32-channel conv_upcat, the patch kernels, conv_pp) the plan sends the layer to one that has (conv_halo_x1_kernel,
+// conv_halo_up_x1_kernel, the 64-channel conv3x3_ring / conv3x3_upcat kernels in X1, conv_igemm_kernel<..., X1>), never to the three-MFMA form.
+// 1: every level-1 layer (112^2 x 64 at 224^2: ring, pool-fused ring, upcat) measured 1.39-1.79x faster in its one-MFMA form at 128 and at 1024 frames, the
+// levels below 1.5-2.2x (profiles/x1_per_launch_x3_vs_x1.txt).  Level 0 (224^2 x 32: enc1_fused, patch, fused tail) is not bound by the matrix pipe.
+constexpr int GEN_X1_FROM = 1;
+
+bool gen_split(const SmirkGeneratorWeights* w) { return w->precision == SMIRK_PRECISION_F16X3 || w->precision == SMIRK_PRECISION_F16X1; }
+
+// level 0..3, 4 = bottleneck + ResNet blocks -> SMIRK_PRECISION_*: what the forward hands to conv_call and what smirk_generator_arith reports
+int gen_level_arith(const SmirkGeneratorWeights* w, int level) {
+    return w->precision == SMIRK_PRECISION_F16X1 ? (level >= GEN_X1_FROM ? SMIRK_PRECISION_F16X1 : SMIRK_PRECISION_F16X3) : w->precision;
+}
+bool gen_level_x1(const SmirkGeneratorWeights* w, int level) { return gen_level_arith(w, level) == SMIRK_PRECISION_F16X1; }
+
 bool gen_args_ok(const SmirkGeneratorWeights* w, int B, int H, int W) {
     if (!w || B <= 0 || H <= 0 || W <= 0 || H % 16 || W % 16) return false;
     if (w->res_blocks < 0 || w->res_blocks > SMIRK_GEN_MAX_RES || w->features <= 0 || w->out_channels <= 0 || w->out_channels > 4) return false;
-    if (w->precision == SMIRK_PRECISION_F16X3) return w->features % 8 == 0 && w->cin_pad == 8 && w->in_channels <= 8;
+    if (gen_split(w)) return w->features % 8 == 0 && w->cin_pad == 8 && w->in_channels <= 8;
     return w->precision == SMIRK_PRECISION_F32 && w->features % 8 == 0 && w->cin_pad % 4 == 0 && w->cin_pad >= w->in_channels;
 }
 
@@ -183,7 +205,7 @@ struct GenPlan {
 GenPlan plan_generator(const SmirkGeneratorWeights* w, int Ca, int Cb, int B, int H, int W, bool taps, int nchain, void* ws) {
     GenPlan p = {};
     SmirkGeneratorPlanReport& r = p.r;
-    const bool split = w->precision == SMIRK_PRECISION_F16X3;
+    const bool split = gen_split(w);
     const int f = w->features;
     p.fast = split && f == 32;
     r.input = Ca == 0 && Cb == 0 ? SMIRK_GEN_INPUT_PACKED : split ? SMIRK_GEN_INPUT_SPLIT_PACK : Cb == 0 ? SMIRK_GEN_INPUT_NHWC_PAD
@@ -197,8 +219,9 @@ GenPlan plan_generator(const SmirkGeneratorWeights* w, int Ca, int Cb, int B, in
     for (int l = 0; l < 4; ++l) {
         const int h = H >> l, wd = W >> l, c = f << l;
         const bool whole = l < GEN_SECTION_FROM;                    // above the section: one launch sequence for the whole batch
+        const bool x3 = split && !gen_level_x1(w, l);               // enc1_fused and the 32-channel conv_upcat exist in the three-MFMA form only
         const SmirkConvDesc conv2 = desc3x3(B, h, wd, c, 0, c, false, true);
-        r.enc[l] = l == 0 && split && smirk_enc1_fused_supported(w->cin_pad, f, h, wd) ? SMIRK_GEN_ENC_ENC1_FUSED
+        r.enc[l] = l == 0 && x3 && smirk_enc1_fused_supported(w->cin_pad, f, h, wd) ? SMIRK_GEN_ENC_ENC1_FUSED
                    : whole && split && smirk_conv3x3_pool_supported(&conv2) ? SMIRK_GEN_ENC_CONV_POOLFUSED : SMIRK_GEN_ENC_CONV_CONV_POOL;
         // Levels 0 / 1 compose their weights inside their own entry.  Levels 2 / 3: the composed weights exist only where the WHOLE batch is eligible (ONE launch builds
         // them ahead of the fork, for every chain to read); a chain takes UPDEEP where they exist and its own frames are eligible, so a batch whose level tensor passes
@@ -207,12 +230,12 @@ GenPlan plan_generator(const SmirkGeneratorWeights* w, int Ca, int Cb, int B, in
         if (composed) r.compose_mask |= 1 << l;
         for (int k = 0; k < SMIRK_GEN_MAX_CHAINS; ++k) {
             if (k >= (whole ? 1 : nchain)) r.dec[l][k] = -1;
-            else if (l < 2) r.dec[l][k] = p.fast && smirk_conv3x3_upcat_eligible(c, h, wd) ? SMIRK_GEN_DEC_UPCAT : SMIRK_GEN_DEC_PAIR;
+            else if (l < 2) r.dec[l][k] = p.fast && (x3 || c == 64) && smirk_conv3x3_upcat_eligible(c, h, wd) ? SMIRK_GEN_DEC_UPCAT : SMIRK_GEN_DEC_PAIR;
             else r.dec[l][k] = composed && smirk_updeep_eligible(whole ? B : r.chain_nb[k], h, wd, c) ? SMIRK_GEN_DEC_UPDEEP : SMIRK_GEN_DEC_PAIR;
         }
     }
     const SmirkConvDesc last = desc3x3(B, H, W, f, 0, f, false, true);
-    r.fused_tail = p.fast && !taps && H >= 64 && smirk_conv3x3_tail_supported(&last, w->out_channels);
+    r.fused_tail = p.fast && !gen_level_x1(w, 0) && !taps && H >= 64 && smirk_conv3x3_tail_supported(&last, w->out_channels);
     // Workspace: the layout depends on neither switches, taps nor chains (callers size and cache workspaces from smirk_generator_workspace_bytes).
     Arena a{(char*)ws, 0};
     p.x = a.take(act_bytes(B, H, W, w->cin_pad));
@@ -249,8 +272,8 @@ void encoder_slots(const Rot& rot, int family, const void* in, void*& t1, void*&
 // encoder level l (smirk_generator.py:52-59): in [h][wd][cin] -> conv -> t1 -> conv -> skip [h][wd][c] -> pool -> pooled
 int encoder_level(const SmirkGeneratorWeights* w, int family, int l, int nb, int h, int wd, int cin, const void* in, void* t1, void* skip, void* pooled, void* tap,
                   void* strm) {
-    const bool split = w->precision == SMIRK_PRECISION_F16X3;
-    const int c = w->features << l;
+    const bool split = gen_split(w);
+    const int c = w->features << l, arith = gen_level_arith(w, l);
     const SmirkConvLayer *c1 = &w->enc[l][0], *c2 = &w->enc[l][1];
     const SmirkConvDesc d1 = desc3x3(nb, h, wd, cin, 0, c, false, true), d2 = desc3x3(nb, h, wd, c, 0, c, false, true);
     switch (family) {
@@ -258,12 +281,12 @@ int encoder_level(const SmirkGeneratorWeights* w, int family, int l, int nb, int
             TRY(smirk_enc1_fused_split16(in, c1->w, c1->scale, c1->shift, c2->w, c2->scale, c2->shift, skip, pooled, nb, h, wd, strm));
             break;
         case SMIRK_GEN_ENC_CONV_POOLFUSED:
-            TRY(conv_call(split, d1, in, nullptr, *c1, nullptr, t1, strm));
-            TRY(smirk_conv3x3_pool_f16x3(&d2, t1, nullptr, c2->w, c2->scale, c2->shift, skip, pooled, strm));
+            TRY(conv_call(arith, d1, in, nullptr, *c1, nullptr, t1, strm));
+            TRY(smirk_conv3x3_pool_launch(&d2, t1, nullptr, c2->w, c2->scale, c2->shift, skip, pooled, strm, arith == SMIRK_PRECISION_F16X1));
             break;
         default:                                                    // SMIRK_GEN_ENC_CONV_CONV_POOL
-            TRY(conv_call(split, d1, in, nullptr, *c1, nullptr, t1, strm));
-            TRY(conv_call(split, d2, t1, nullptr, *c2, nullptr, skip, strm));
+            TRY(conv_call(arith, d1, in, nullptr, *c1, nullptr, t1, strm));
+            TRY(conv_call(arith, d2, t1, nullptr, *c2, nullptr, skip, strm));
             break;
     }
     tap_copy(tap, skip, act_bytes(nb, h, wd, c), strm);
@@ -283,21 +306,20 @@ void decoder_slots(const Rot& rot, int family, const void* coarse, void*& tmp, v
 // tmp holds `up` (PAIR) or the coarse launch's partial sums (UPDEEP)
 int decoder_level(const SmirkGeneratorWeights* w, const GenPlan& p, int family, int l, int nb, int h, int wd, const void* coarse, const void* skip, void* tmp,
                   void* out, void* strm) {
-    const bool split = w->precision == SMIRK_PRECISION_F16X3;
-    const int c = w->features << l;
+    const int c = w->features << l, arith = gen_level_arith(w, l);
     const SmirkConvLayer &up = w->up[3 - l], &conv = w->dec[3 - l][0];
     switch (family) {
         case SMIRK_GEN_DEC_UPCAT:
-            return smirk_conv3x3_upcat_launch(c, coarse, skip, &up, &conv, out, nb, h, wd, p.upcat_w[l], p.upcat_s[l], (hipStream_t)strm);
+            return smirk_conv3x3_upcat_launch(c, coarse, skip, &up, &conv, out, nb, h, wd, p.upcat_w[l], p.upcat_s[l], (hipStream_t)strm, arith == SMIRK_PRECISION_F16X1);
         case SMIRK_GEN_DEC_UPDEEP: {                                // launch 2 is the ordinary 3x3 convolution over the skip tensor with launch 1's output as its residual
             const SmirkUpdeepLevel u = updeep_level(w, p, l);
-            TRY(smirk_updeep_coarse_launch(&u, coarse, tmp, nb, h, wd, (hipStream_t)strm));
+            TRY(smirk_updeep_coarse_launch(&u, coarse, tmp, nb, h, wd, arith == SMIRK_PRECISION_F16X1, (hipStream_t)strm));
             const SmirkConvLayer half{u.wskip, conv.scale, conv.shift};
-            return conv_call(true, desc3x3(nb, h, wd, c, 0, c, false, true), skip, nullptr, half, tmp, out, strm);
+            return conv_call(arith, desc3x3(nb, h, wd, c, 0, c, false, true), skip, nullptr, half, tmp, out, strm);
         }
         default:                                                    // SMIRK_GEN_DEC_PAIR
-            TRY(conv_call(split, desc1x1(nb, h / 2, wd / 2, 2 * c, c, false, true), coarse, nullptr, up, nullptr, tmp, strm));
-            return conv_call(split, desc3x3(nb, h, wd, c, c, c, false, true), tmp, skip, conv, nullptr, out, strm);
+            TRY(conv_call(arith, desc1x1(nb, h / 2, wd / 2, 2 * c, c, false, true), coarse, nullptr, up, nullptr, tmp, strm));
+            return conv_call(arith, desc3x3(nb, h, wd, c, c, c, false, true), tmp, skip, conv, nullptr, out, strm);
     }
 }
 
@@ -310,10 +332,20 @@ extern "C" size_t smirk_generator_workspace_bytes(const SmirkGeneratorWeights* w
 
 extern "C" int smirk_genplan_abi_version(void) { return SMIRK_GENPLAN_ABI_VERSION; }
 
+extern "C" int smirk_genarith_abi_version(void) { return SMIRK_GENARITH_ABI_VERSION; }
+
+extern "C" int smirk_generator_arith(const SmirkGeneratorWeights* w, int32_t* x1_from, int32_t level_arith[4], int32_t* deep_arith) {
+    if (!w || !x1_from || !level_arith || !deep_arith || (!gen_split(w) && w->precision != SMIRK_PRECISION_F32)) return SMIRK_ERR_BAD_ARG;
+    *x1_from = GEN_X1_FROM;
+    for (int l = 0; l < 4; ++l) level_arith[l] = gen_level_arith(w, l);
+    *deep_arith = gen_level_arith(w, 4);
+    return SMIRK_OK;
+}
+
 extern "C" int smirk_generator_plan(const SmirkGeneratorWeights* w, int Ca, int Cb, int B, int H, int W, int with_taps, SmirkGeneratorPlanReport* report) {
     if (!gen_args_ok(w, B, H, W) || !report) return SMIRK_ERR_BAD_ARG;
     const bool packed = Ca == 0 && Cb == 0;
-    if (packed ? w->precision != SMIRK_PRECISION_F16X3 : (Ca <= 0 || Cb < 0 || Ca + Cb != w->in_channels)) return SMIRK_ERR_BAD_ARG;
+    if (packed ? !gen_split(w) : (Ca <= 0 || Cb < 0 || Ca + Cb != w->in_channels)) return SMIRK_ERR_BAD_ARG;
     *report = plan_generator(w, Ca, Cb, B, H, W, with_taps != 0, gen_chain_wish(w, B, H, W, with_taps != 0), nullptr).r;
     return report->input < 0 ? SMIRK_ERR_UNSUPPORTED : SMIRK_OK;
 }
@@ -329,8 +361,8 @@ static int generator_forward_body(const SmirkGeneratorWeights* w, const float* a
     const ChainGrant cg = grant_chains(wish, (hipStream_t)stream);
     if (cg.n != wish) p = plan_generator(w, Ca, Cb, B, H, W, taps != nullptr, cg.n, ws);
     const SmirkGeneratorPlanReport& r = p.r;
-    const bool split = w->precision == SMIRK_PRECISION_F16X3;
-    const int f = w->features, L0 = GEN_SECTION_FROM;
+    const bool split = gen_split(w);
+    const int f = w->features, L0 = GEN_SECTION_FROM, deep = gen_level_arith(w, 4);
     auto tap = [&](int i) { return taps ? taps[i] : nullptr; };
 
     // ---- cat + NCHW -> NHWC (+ split) of the network input (smirk_trainer.py:94, demo.py:167), and the composed weights of the deep decoder levels ------------------
@@ -378,16 +410,16 @@ static int generator_forward_body(const SmirkGeneratorWeights* w, const float* a
             cur = P(pl); cur_slot = pl;
         }
         void* b1 = p.rot.pick(cur_slot, nullptr);                   // bottleneck
-        TRY(conv_call(split, desc3x3(nb, h16, w16, c16 / 2, 0, c16, false, true), cur, nullptr, w->enc[4][0], nullptr, P(b1), strm));
+        TRY(conv_call(deep, desc3x3(nb, h16, w16, c16 / 2, 0, c16, false, true), cur, nullptr, w->enc[4][0], nullptr, P(b1), strm));
         void* b2 = p.rot.pick(b1, nullptr);
-        TRY(conv_call(split, desc3x3(nb, h16, w16, c16, 0, c16, false, true), P(b1), nullptr, w->enc[4][1], nullptr, P(b2), strm));
+        TRY(conv_call(deep, desc3x3(nb, h16, w16, c16, 0, c16, false, true), P(b1), nullptr, w->enc[4][1], nullptr, P(b2), strm));
         tap_copy(tap(4), b2, act_bytes(B, h16, w16, c16), strm);
         const void* dc = b2;                                        // ResNet blocks: reflect pad, conv-BN-ReLU, reflect pad, conv-BN, + x
         for (int i = 0; i < w->res_blocks; ++i) {
             void* t = p.rot.pick(dc, nullptr);
-            TRY(conv_call(split, desc3x3(nb, h16, w16, c16, 0, c16, true, true), P(dc), nullptr, w->res[i][0], nullptr, P(t), strm));
+            TRY(conv_call(deep, desc3x3(nb, h16, w16, c16, 0, c16, true, true), P(dc), nullptr, w->res[i][0], nullptr, P(t), strm));
             void* o = p.rot.pick(dc, t);
-            TRY(conv_call(split, desc3x3(nb, h16, w16, c16, 0, c16, true, false), P(t), nullptr, w->res[i][1], P(dc), P(o), strm));
+            TRY(conv_call(deep, desc3x3(nb, h16, w16, c16, 0, c16, true, false), P(t), nullptr, w->res[i][1], P(dc), P(o), strm));
             dc = o;
         }
         tap_copy(tap(5), dc, act_bytes(B, h16, w16, c16), strm);
@@ -398,7 +430,7 @@ static int generator_forward_body(const SmirkGeneratorWeights* w, const float* a
             TRY(decoder_level(w, p, r.dec[l][k], l, nb, h, wd, P(dc), N(p.e[l], h, wd, c), P(tmp), P(d1), strm));
             const bool last = l == L0;
             void* d2 = last ? p.rot.pick(d1, in) : p.rot.pick(d1, nullptr);
-            TRY(conv_call(split, desc3x3(nb, h, wd, c, 0, c, false, true), P(d1), nullptr, w->dec[3 - l][1], nullptr, last ? N(d2, h, wd, c) : P(d2), strm));
+            TRY(conv_call(gen_level_arith(w, l), desc3x3(nb, h, wd, c, 0, c, false, true), P(d1), nullptr, w->dec[3 - l][1], nullptr, last ? N(d2, h, wd, c) : P(d2), strm));
             tap_copy(tap(6 + (3 - l)), d2, act_bytes(B, h, wd, c), strm);
             dc = d2;
         }
@@ -438,7 +470,7 @@ static int generator_forward_body(const SmirkGeneratorWeights* w, const float* a
         const SmirkConvDesc d2 = desc3x3(B, h, wd, c, 0, c, false, true);
         if (l == 0 && r.fused_tail) return smirk_conv3x3_tail_f16x3(&d2, t1, nullptr, c2.w, c2.scale, c2.shift, w->final_w, w->final_b, y, w->out_channels, stream);
         void* t2 = p.rot.pick(t1, nullptr);
-        TRY(conv_call(split, d2, t1, nullptr, c2, nullptr, t2, stream));
+        TRY(conv_call(gen_level_arith(w, l), d2, t1, nullptr, c2, nullptr, t2, stream));
         tap_copy(tap(6 + (3 - l)), t2, act_bytes(B, h, wd, c), stream);
         dcur = t2;
     }
@@ -455,7 +487,7 @@ extern "C" int smirk_generator_forward(const SmirkGeneratorWeights* w, const flo
 
 extern "C" int smirk_generator_forward_packed(const SmirkGeneratorWeights* w, const void* packed, float* y, int B, int H, int W, void* const* taps, void* ws,
                                               size_t ws_bytes, void* stream) {
-    if (!gen_args_ok(w, B, H, W) || w->precision != SMIRK_PRECISION_F16X3 || !packed || !y || !ws) return SMIRK_ERR_BAD_ARG;
+    if (!gen_args_ok(w, B, H, W) || !gen_split(w) || !packed || !y || !ws) return SMIRK_ERR_BAD_ARG;
     if (!w->final_w || !w->final_b) return SMIRK_ERR_BAD_ARG;
     return generator_forward_body(w, nullptr, 0, nullptr, 0, packed, y, B, H, W, taps, ws, ws_bytes, stream);
 }
@@ -569,7 +601,7 @@ extern "C" int smirk_backbone_forward(const SmirkBackboneWeights* w, const float
     for (int i = 0; i < 3; ++i) rot.slot[i] = (char*)ws + p.slot_off[i];
     float* pooled = (float*)((char*)ws + p.pooled_off);
     auto pointwise = [&](const void* in, int hh, int ww, int cin, int cout, const SmirkConvLayer& L, bool relu, const void* res, void* o) {
-        return conv_call(split, desc1x1(B, hh, ww, cin, cout, relu, false), in, nullptr, L, res, o, stream);
+        return conv_call(w->precision, desc1x1(B, hh, ww, cin, cout, relu, false), in, nullptr, L, res, o, stream);
     };
     auto depthwise = [&](const void* in, int hh, int ww, int c, int stride, const SmirkConvLayer& L, void* o) {
         return split ? smirk_dwconv3x3_split16(in, (const float*)L.w, L.scale, L.shift, o, B, hh, ww, c, stride, 1, stream)

@@ -7,10 +7,13 @@ per-stream workspace, every 3x3 / transposed convolution on the MFMA implicit-GE
 fused in the epilogue, reflection padding and the decoder's channel concat done as address arithmetic, 2x2 max-pool as a vectorised streaming
 kernel, and the network tail (dec1conv2 + BN + ReLU + 1x1 conv + sigmoid) fused into one launch.
 
-Two arithmetic modes (`SmirkGenerator.precision`, default from $SMIRK_AMD_GENERATOR_PRECISION or "f16x3"):
+Three arithmetic modes (`SmirkGenerator.precision`, default from $SMIRK_AMD_GENERATOR_PRECISION or "f16x3"):
   "f16x3"  split-fp16: activations/weights carried as fp16 (hi, lo) pairs, 3 fp16 MFMAs per product with fp32 accumulation —
            fp32-class accuracy (same error vs fp64 as an fp32 GEMM) at the 16-bit matrix rate; CDNA4 has no TF32.
   "f32"    exact fp32 FMA chain on v_mfma_f32_32x32x2_f32 (157 TFLOP/s peak).
+  "f16x1"  eval-mode inference only: the storage of "f16x3" (same weight images, workspace and range audit), ONE fp16 MFMA per product block on the hi halves
+           in every convolution of the matrix-bound levels (smirk_generator_arith names them; the levels above run the launches of "f16x3") — the 16-bit
+           class the reference reaches under autocast, NOT fp32-class accuracy.  Train mode and eval-mode input gradients ignore it: `train_arith` decides theirs.
 Train mode (`.train()`): batch-statistics BatchNorm + a full backward pass, see smirk_amd/generator_train.py (BASELINE config 5, generator slice).
 """
 import os
@@ -72,6 +75,9 @@ def _pack3x3(w, cin_pad=None):
     return w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()
 
 
+SPLIT_PRECISIONS = ("f16x3", "f16x1")                                 # the modes stored as split-fp16 (hi, lo) pairs: everything but the MFMA count is shared
+
+
 class SmirkGenerator(nn.Module):
     """Drop-in for src/smirk_generator.py:SmirkGenerator (same constructor, state_dict keys and forward).  Limits of the gfx950 kernels, all reported by
     exceptions: init_features % 8 == 0 and out_channels <= 4 (constructor); input H, W multiples of 16 (the reference's own skip `torch.cat` fails otherwise);
@@ -118,9 +124,9 @@ class SmirkGenerator(nn.Module):
         key = self._key()
         if self._packed is not None and self._packed_key == key:
             return self._packed
-        if self.precision not in ("f16x3", "f32"):
+        if self.precision not in SPLIT_PRECISIONS + ("f32",):
             raise L.SmirkHipError(f"unknown SmirkGenerator.precision {self.precision!r}")
-        split = self.precision == "f16x3"
+        split = self.precision in SPLIT_PRECISIONS
         if split and self.in_channels > 8:
             # the reference accepts any in_channels: more than one 8-channel group at the input takes the exact-fp32 MFMA kernels instead of being refused
             # (same tolerances, ~2x slower; init_features % 8 is the remaining requirement, checked in __init__)
@@ -175,7 +181,7 @@ class SmirkGenerator(nn.Module):
             raise L.SmirkHipError(f"at most {L.GEN_MAX_RES} ResNet blocks")
         w = L.SmirkGeneratorWeights()
         w.in_channels, w.out_channels, w.features, w.res_blocks = self.in_channels, self.out_channels, self.features, len(self.resnet_blocks)
-        w.precision = L.PRECISION_F16X3 if self._split else L.PRECISION_F32
+        w.precision = L.PRECISION_F32 if not self._split else L.PRECISION_F16X1 if self.precision == "f16x1" else L.PRECISION_F16X3
         w.cin_pad = self._cin_pad
         for l, tag in enumerate(("enc1", "enc2", "enc3", "enc4", "bottleneck")):
             w.enc[l][0], w.enc[l][1] = L.conv_layer(*P[tag + "1"]), L.conv_layer(*P[tag + "2"])
@@ -197,7 +203,7 @@ class SmirkGenerator(nn.Module):
         if self.training:
             # train mode (smirk_trainer.py:349-355 calls self.train() before every step): batch-statistics BatchNorm with running-stat updates and a
             # real backward pass — one autograd.Function over the whole network (smirk_amd/generator_train.py, csrc/train.hip, csrc/wgrad.hip)
-            if self.precision != "f16x3":
+            if self.precision not in SPLIT_PRECISIONS:                       # ("f16x1" is an inference precision: `train_arith` alone decides the arithmetic here)
                 raise L.SmirkHipError("train mode runs in the split-fp16 ('f16x3') arithmetic mode")
             if self.in_channels > 8:
                 raise L.SmirkHipError("smirk_amd.SmirkGenerator: train mode / backward need in_channels <= 8 (one split16 channel group at the network input); "
@@ -207,7 +213,7 @@ class SmirkGenerator(nn.Module):
             return GeneratorTrainFunction.apply(self, x, *self.parameters())
         srcs = [a] + ([] if b is None else [b])
         wants_input_grad = taps is None and torch.is_grad_enabled() and any(t.requires_grad for t in srcs)
-        if wants_input_grad and (self.precision != "f16x3" or self.in_channels > 8):
+        if wants_input_grad and (self.precision not in SPLIT_PRECISIONS or self.in_channels > 8):
             # decided on the EFFECTIVE arithmetic (in_channels > 8 runs the exact-fp32 kernels even when precision == "f16x3"): say so now instead of failing
             # inside the autograd function or handing back a tensor whose backward raises later
             raise L.SmirkHipError("smirk_amd.SmirkGenerator: a gradient with respect to the input is available in the split-fp16 ('f16x3') mode with "
@@ -261,7 +267,7 @@ class SmirkGenerator(nn.Module):
 
     def accepts_packed(self):
         """True where forward_packed serves this module: eval mode, split-fp16 arithmetic, the 3 + 3 input channels of cat(rendered_img, masked_img)."""
-        return not self.training and self.precision == "f16x3" and self.in_channels == 6
+        return not self.training and self.precision in SPLIT_PRECISIONS and self.in_channels == 6
 
     def forward_packed(self, packed, _taps=None):
         """forward_pair(rendered, masked) from the packed split-fp16 network input [B,H,W,8] that masking.demo_masked_image_packed wrote (channels 0-2
@@ -269,7 +275,7 @@ class SmirkGenerator(nn.Module):
         bits.  Inference in the split-fp16 mode only; no gradient flows into `packed`."""
         L.raise_if_range_tripped("smirk_amd.SmirkGenerator.forward_packed")
         if not self.accepts_packed():
-            raise L.SmirkHipError("smirk_amd.SmirkGenerator.forward_packed runs in eval mode with precision 'f16x3' and in_channels == 6 only "
+            raise L.SmirkHipError("smirk_amd.SmirkGenerator.forward_packed runs in eval mode with precision 'f16x3' / 'f16x1' and in_channels == 6 only "
                                   "(training=%r, precision=%r, in_channels=%d)" % (self.training, self.precision, self.in_channels))
         if packed.dim() != 4 or packed.shape[3] != 8:
             raise L.SmirkHipError("expected the packed network input [B,H,W,8]")
