@@ -54,6 +54,8 @@ from .vgg_loss import VGGPerceptualLoss  # noqa: E402,F401  (smirk_trainer.py:10
 from .mica import MICA, MappingNetwork  # noqa: E402,F401  (smirk_trainer.py:128-131: the pre-training stage's shape term; drop-in for src.models.MICA.mica)
 from .expression_loss import ExpressionLoss  # noqa: E402,F401  (smirk_trainer.py:108-119: the first path's emotion term; drop-in for src.losses.ExpressionLoss)
 from .optim import Adam, clip_grad_norm_  # noqa: E402,F401  (smirk_trainer.py:379, base_trainer.py:51,62,123-127: the gradient clip and the Adam steps)
+from . import data  # noqa: E402,F401  (datasets/base_dataset.py:124-215: prepare_data for a whole batch)
+from .data import AugmentConfig, BatchPreparer  # noqa: E402,F401
 
 
 def check_numerics():
@@ -66,4 +68,4 @@ def check_numerics():
 
 __all__ = ["FLAME", "Renderer", "SmirkEncoder", "SmirkGenerator", "SmirkHipError", "lib", "masking", "VideoPipeline", "check_numerics", "TemplateBank", "augment_flame_params",
            "load_templates", "FirstPathLoss", "LossTerms", "weighted_loss", "losses", "first_path", "VGGPerceptualLoss", "MICA", "MappingNetwork", "ExpressionLoss", "Adam",
-           "clip_grad_norm_"]
+           "clip_grad_norm_", "data", "AugmentConfig", "BatchPreparer"]

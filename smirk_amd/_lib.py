@@ -313,6 +313,44 @@ GENARITH_SIGS = {
 }
 GENARITH_EXPORTS = tuple(GENARITH_SIGS)
 
+# The extension table of include/smirk_data.h (the trainer's batch preparation: decoded frames + landmark arrays -> the batch dict on the device): the same shared
+# object, a version of its own.
+DATA_ABI_VERSION = 1
+DATA_MAX_POINTS, DATA_FAN_POINTS, DATA_MICA_SIZE, DATA_MAX_SIZE = 1024, 68, 112, 2040   # include/smirk_data.h SMIRK_DATA_MAX_POINTS, _FAN_POINTS, _MICA_SIZE, _MAX_SIZE
+DATA_TRANSFORMS = ("brightness_contrast", "gamma", "color_jitter", "clahe", "rgb_shift", "blur", "gauss_noise", "shift_scale_rotate")   # enum SmirkDataTransform, by code
+
+
+class SmirkDataAugment(C.Structure):
+    _fields_ = [("p", C.c_double * 8)] + \
+               [(n, C.c_double) for n in ("brightness_limit", "contrast_limit", "gamma_lo", "gamma_hi", "cj_brightness", "cj_contrast", "cj_saturation", "cj_hue",
+                                          "clahe_lo", "clahe_hi", "rgb_shift", "noise_var_lo", "noise_var_hi", "shift_limit", "scale_limit", "rotate_limit")] + \
+               [("blur_max", C.c_int32), ("_pad", C.c_int32)]
+
+
+class SmirkDataFrame(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("H", C.c_int32), ("W", C.c_int32)]
+
+
+class SmirkDataParams(C.Structure):
+    _fields_ = [(n, C.c_double * 6) for n in ("crop_fwd", "crop_inv", "ssr_fwd", "ssr_inv", "mica_inv")] + \
+               [(n, C.c_double) for n in ("scale", "bc_alpha", "bc_beta", "gamma")] + [("cj", C.c_double * 4), ("clahe_clip", C.c_double), ("rgb_shift", C.c_double * 3)] + \
+               [(n, C.c_double) for n in ("noise_sigma", "ssr_angle", "ssr_scale", "ssr_dx", "ssr_dy")] + \
+               [(n, C.c_int32) for n in ("coins", "blur_k", "flag_fan", "_pad")]
+
+
+DATA_SIGS = {
+    "smirk_data_abi_version": (_i, []),
+    "smirk_data_workspace_bytes": (_sz, [_i, _i, _i]),
+    "smirk_data_hull_points_offset": (_sz, [_i, _i, _i]),
+    "smirk_data_hull_offset": (_sz, [_i, _i, _i]),
+    "smirk_data_params": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _i, C.c_double, C.c_double, C.POINTER(SmirkDataAugment), C.c_uint64, C.c_uint64, _p, _p, _p, _p, _sz, _p]),
+    "smirk_data_crop": (_i, [_p, _sz, _p, _i, _i, _i, _p, _p, _p, _sz, _p]),
+    "smirk_data_stats": (_i, [_i, _i, _p, _sz, _p]),
+    "smirk_data_colour": (_i, [_i, _i, _p, _sz, _p]),
+    "smirk_data_finish": (_i, [_i, _i, C.c_uint64, C.c_uint64, _p, _p, _p, _sz, _p]),
+}
+DATA_EXPORTS = tuple(DATA_SIGS)
+
 _LIB = None
 
 
@@ -328,13 +366,13 @@ def lib():
             raise SmirkHipError(f"{LIB_PATH} not found: build it with `python -m smirk_amd.build` "
                                 "(smirk_amd has no CPU / eager fallback)")
         L = C.CDLL(LIB_PATH)
-        for table in (_SIGS, MICA_SIGS, EMOTION_SIGS, OPTIM_SIGS, HANDOFF_SIGS, GENPLAN_SIGS, GENARITH_SIGS):
+        for table in (_SIGS, MICA_SIGS, EMOTION_SIGS, OPTIM_SIGS, HANDOFF_SIGS, GENPLAN_SIGS, GENARITH_SIGS, DATA_SIGS):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)       # AttributeError => header / library mismatch
                 fn.restype, fn.argtypes = res, args
         if L.smirk_abi_version() != ABI_VERSION or L.smirk_mica_abi_version() != MICA_ABI_VERSION or L.smirk_emotion_abi_version() != EMOTION_ABI_VERSION or \
                 L.smirk_optim_abi_version() != OPTIM_ABI_VERSION or L.smirk_handoff_abi_version() != HANDOFF_ABI_VERSION or \
-                L.smirk_genplan_abi_version() != GENPLAN_ABI_VERSION or L.smirk_genarith_abi_version() != GENARITH_ABI_VERSION:
+                L.smirk_genplan_abi_version() != GENPLAN_ABI_VERSION or L.smirk_genarith_abi_version() != GENARITH_ABI_VERSION or L.smirk_data_abi_version() != DATA_ABI_VERSION:
             raise SmirkHipError("libsmirk_hip.so ABI version mismatch; rebuild")
         _LIB = L
     return _LIB
