@@ -56,6 +56,8 @@ from .expression_loss import ExpressionLoss  # noqa: E402,F401  (smirk_trainer.p
 from .optim import Adam, clip_grad_norm_  # noqa: E402,F401  (smirk_trainer.py:379, base_trainer.py:51,62,123-127: the gradient clip and the Adam steps)
 from . import data  # noqa: E402,F401  (datasets/base_dataset.py:124-215: prepare_data for a whole batch)
 from .data import AugmentConfig, BatchPreparer  # noqa: E402,F401
+from . import visualize  # noqa: E402,F401  (base_trainer.py:130-224: the visualisation sheet, written on the device)
+from .visualize import create_visualizations, save_visualizations  # noqa: E402,F401
 
 
 def check_numerics():
@@ -68,4 +70,4 @@ def check_numerics():
 
 __all__ = ["FLAME", "Renderer", "SmirkEncoder", "SmirkGenerator", "SmirkHipError", "lib", "masking", "VideoPipeline", "check_numerics", "TemplateBank", "augment_flame_params",
            "load_templates", "FirstPathLoss", "LossTerms", "weighted_loss", "losses", "first_path", "VGGPerceptualLoss", "MICA", "MappingNetwork", "ExpressionLoss", "Adam",
-           "clip_grad_norm_", "data", "AugmentConfig", "BatchPreparer"]
+           "clip_grad_norm_", "data", "AugmentConfig", "BatchPreparer", "visualize", "create_visualizations", "save_visualizations"]

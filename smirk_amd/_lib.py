@@ -351,6 +351,31 @@ DATA_SIGS = {
 }
 DATA_EXPORTS = tuple(DATA_SIGS)
 
+# The extension table of include/smirk_visual.h (the trainer's visualisation sheet: fp32 panels on the device -> one uint8 sheet): the same shared object, a version
+# of its own.
+VISUAL_ABI_VERSION = 1
+VISUAL_MAX_COLUMNS, VISUAL_MAX_POINTS, VISUAL_LAYERS = 16, 1024, 4     # include/smirk_visual.h SMIRK_VISUAL_MAX_COLUMNS, _MAX_POINTS, _LAYERS
+VISUAL_MIN_SIZE, VISUAL_MAX_SIZE, VISUAL_PADDING = 8, 4096, 2           # SMIRK_VISUAL_MIN_SIZE, _MAX_SIZE, _PADDING
+
+
+class SmirkVisualColumn(C.Structure):
+    _fields_ = [("src", _p * 4), ("blend", _p), ("w_src", C.c_float), ("w_blend", C.c_float)] + \
+               [(n, C.c_int32) for n in ("nsrc", "channels", "Hs", "Ws", "nrow", "landmarks")]
+
+
+class SmirkVisualDots(C.Structure):
+    _fields_ = [("lm", _p * 4), ("rows", C.c_int32 * 4), ("npts", C.c_int32 * 4)]
+
+
+VISUAL_SIGS = {
+    "smirk_visual_abi_version": (_i, []),
+    "smirk_visual_sheet_size": (_i, [C.POINTER(SmirkVisualColumn), _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_sz)]),
+    "smirk_visual_workspace_bytes": (_sz, [_i, _i]),
+    "smirk_visual_dots": (_i, [C.POINTER(SmirkVisualDots), _i, _i, C.c_float, _p, _sz, _p]),
+    "smirk_visual_sheet": (_i, [C.POINTER(SmirkVisualColumn), _i, _i, _i, _i, _p, _sz, _p, _sz, _p]),
+}
+VISUAL_EXPORTS = tuple(VISUAL_SIGS)
+
 _LIB = None
 
 
@@ -366,13 +391,14 @@ def lib():
             raise SmirkHipError(f"{LIB_PATH} not found: build it with `python -m smirk_amd.build` "
                                 "(smirk_amd has no CPU / eager fallback)")
         L = C.CDLL(LIB_PATH)
-        for table in (_SIGS, MICA_SIGS, EMOTION_SIGS, OPTIM_SIGS, HANDOFF_SIGS, GENPLAN_SIGS, GENARITH_SIGS, DATA_SIGS):
+        for table in (_SIGS, MICA_SIGS, EMOTION_SIGS, OPTIM_SIGS, HANDOFF_SIGS, GENPLAN_SIGS, GENARITH_SIGS, DATA_SIGS, VISUAL_SIGS):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)       # AttributeError => header / library mismatch
                 fn.restype, fn.argtypes = res, args
         if L.smirk_abi_version() != ABI_VERSION or L.smirk_mica_abi_version() != MICA_ABI_VERSION or L.smirk_emotion_abi_version() != EMOTION_ABI_VERSION or \
                 L.smirk_optim_abi_version() != OPTIM_ABI_VERSION or L.smirk_handoff_abi_version() != HANDOFF_ABI_VERSION or \
-                L.smirk_genplan_abi_version() != GENPLAN_ABI_VERSION or L.smirk_genarith_abi_version() != GENARITH_ABI_VERSION or L.smirk_data_abi_version() != DATA_ABI_VERSION:
+                L.smirk_genplan_abi_version() != GENPLAN_ABI_VERSION or L.smirk_genarith_abi_version() != GENARITH_ABI_VERSION or L.smirk_data_abi_version() != DATA_ABI_VERSION or \
+                L.smirk_visual_abi_version() != VISUAL_ABI_VERSION:
             raise SmirkHipError("libsmirk_hip.so ABI version mismatch; rebuild")
         _LIB = L
     return _LIB

@@ -27,7 +27,8 @@ ARCH = "gfx950"
 COMMON = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-Wall", "-Wno-unused-function", "-fno-slp-vectorize", "-fno-vectorize"]
 # optim.hip: torch's Adam rounds every product and sum on its own (include/smirk_optim.h)
 PER_FILE = {"render.hip": ["-ffp-contract=off"], "video.hip": ["-ffp-contract=off"], "optim.hip": ["-ffp-contract=off"],
-            "data.hip": ["-ffp-contract=off"]}        # data.hip: float64 arithmetic restated product by product in tests/data_law.py
+            "data.hip": ["-ffp-contract=off"],        # data.hip: float64 arithmetic restated product by product in tests/data_law.py
+            "visual.hip": ["-ffp-contract=off"]}      # visual.hip: float32 arithmetic restated operation by operation in tests/visual_law.py
 
 
 def sources():
@@ -45,7 +46,7 @@ def build(force=False, verbose=True):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(LIBDIR, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    headers += [os.path.join(os.path.dirname(HERE), "include", f) for f in ("smirk_hip.h", "smirk_mica.h", "smirk_emotion.h", "smirk_optim.h", "smirk_handoff.h", "smirk_generator_plan.h", "smirk_generator_arith.h", "smirk_data.h")]
+    headers += [os.path.join(os.path.dirname(HERE), "include", f) for f in ("smirk_hip.h", "smirk_mica.h", "smirk_emotion.h", "smirk_optim.h", "smirk_handoff.h", "smirk_generator_plan.h", "smirk_generator_arith.h", "smirk_data.h", "smirk_visual.h")]
     objs, jobs = [], []
     for s in sources():
         src = os.path.join(CSRC, s)
