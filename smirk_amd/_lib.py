@@ -282,6 +282,17 @@ HANDOFF_SIGS = {
 }
 HANDOFF_EXPORTS = tuple(HANDOFF_SIGS)
 
+# The extension table of include/smirk_train_handoff.h (sampled points -> generator input of the two training paths: one launch for the points of the source frame
+# and its Ke target frames, one for the transfer, masked_img and the generator's packed input): the same shared object, a version of its own.
+TRAIN_HANDOFF_ABI_VERSION = 1
+RENDERED_RULES = ("nonzero", "positive")                               # SMIRK_RENDERED_RULE_*, by code
+TRAIN_HANDOFF_SIGS = {
+    "smirk_train_handoff_abi_version": (_i, []),
+    "smirk_sample_transfer_points": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, C.c_uint64, C.c_uint64, _p, _p, _p, _p, _p, _p, _p]),
+    "smirk_train_masking_handoff": (_i, [_p, _p, _p, _ll, _p, _p, _i, _i, _i, _i, _i, _i, C.c_float, C.c_uint64, C.c_uint64, C.c_uint64, _p, _p, _p]),
+}
+TRAIN_HANDOFF_EXPORTS = tuple(TRAIN_HANDOFF_SIGS)
+
 # The extension table of include/smirk_generator_plan.h (what a whole-network generator entry would launch, answered by generator_plan without touching device
 # memory; for tests and tools, nothing on the hot path calls it): the same shared object, a version of its own.
 GENPLAN_ABI_VERSION = 1
@@ -391,14 +402,14 @@ def lib():
             raise SmirkHipError(f"{LIB_PATH} not found: build it with `python -m smirk_amd.build` "
                                 "(smirk_amd has no CPU / eager fallback)")
         L = C.CDLL(LIB_PATH)
-        for table in (_SIGS, MICA_SIGS, EMOTION_SIGS, OPTIM_SIGS, HANDOFF_SIGS, GENPLAN_SIGS, GENARITH_SIGS, DATA_SIGS, VISUAL_SIGS):
+        for table in (_SIGS, MICA_SIGS, EMOTION_SIGS, OPTIM_SIGS, HANDOFF_SIGS, TRAIN_HANDOFF_SIGS, GENPLAN_SIGS, GENARITH_SIGS, DATA_SIGS, VISUAL_SIGS):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)       # AttributeError => header / library mismatch
                 fn.restype, fn.argtypes = res, args
         if L.smirk_abi_version() != ABI_VERSION or L.smirk_mica_abi_version() != MICA_ABI_VERSION or L.smirk_emotion_abi_version() != EMOTION_ABI_VERSION or \
                 L.smirk_optim_abi_version() != OPTIM_ABI_VERSION or L.smirk_handoff_abi_version() != HANDOFF_ABI_VERSION or \
                 L.smirk_genplan_abi_version() != GENPLAN_ABI_VERSION or L.smirk_genarith_abi_version() != GENARITH_ABI_VERSION or L.smirk_data_abi_version() != DATA_ABI_VERSION or \
-                L.smirk_visual_abi_version() != VISUAL_ABI_VERSION:
+                L.smirk_visual_abi_version() != VISUAL_ABI_VERSION or L.smirk_train_handoff_abi_version() != TRAIN_HANDOFF_ABI_VERSION:
             raise SmirkHipError("libsmirk_hip.so ABI version mismatch; rebuild")
         _LIB = L
     return _LIB

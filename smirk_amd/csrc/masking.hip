@@ -8,10 +8,13 @@
 //   points_to_pixels    .5*(1+p)*S -> int64 (truncation) -> clamp x,y                          (masking.py:172-175)
 //   maxpool_sq          (2r+1)^2 stride-1 max pool with -inf padding as two separable passes   (masking.py:78,96)
 //   bernoulli_field / masking_compose / transfer_pixels                                        (masking.py:71-102,116-129)
+//   masking_handoff / sample_transfer_points + train_masking_handoff     the chains above fused for the inference path (smirk_handoff.h) and
+//                       for the trainer's two paths (smirk_train_handoff.h): same draws, same bits, the generator's packed input stored beside
 // Random draws are reproducible from (seed, call offset) but are NOT torch's CPU/CUDA streams — the reference itself draws
 // different numbers on CPU and GPU; deterministic entry points (coords= / explicit fields) are what the parity tests pin.
 #include "conv_common.h"
 #include "../../include/smirk_handoff.h"
+#include "../../include/smirk_train_handoff.h"
 
 // ---- Philox4x32-10 (Salmon et al. 2011), counter = (idx, stream, 0, 0), key = seed ------------------------------------------------
 __device__ __forceinline__ void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
@@ -43,13 +46,10 @@ __global__ __launch_bounds__(256) void mask_face_weights_kernel(const float* __r
     w[i] = p * area;
 }
 
-__global__ __launch_bounds__(1024) void sample_faces_kernel(const float* __restrict__ w, int F, int num, uint64_t seed,
-                                                            uint64_t offset, int32_t* __restrict__ idx, float* __restrict__ bary) {
-    extern __shared__ float cdf[];               // [F] inclusive prefix sums, + 32 wave totals
-    float* wtot = cdf + F;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
-    const float* wb = w + (size_t)b * F;
-    // block scan in chunks of blockDim: sequential carry keeps the summation order fixed (deterministic)
+// The CDF of one frame's face weights into LDS: cdf [F] inclusive prefix sums, wtot [blockDim / 64] wave totals.  Returns the total.  Block scan in chunks of
+// blockDim: the sequential carry keeps the summation order fixed (deterministic).  Shared by sample_faces_kernel and sample_transfer_points_kernel.
+__device__ __forceinline__ float face_cdf_scan(const float* __restrict__ wb, int F, float* cdf, float* wtot) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
     float carry = 0.f;
     for (int base = 0; base < F; base += blockDim.x) {
         const int i = base + tid;
@@ -66,19 +66,32 @@ __global__ __launch_bounds__(1024) void sample_faces_kernel(const float* __restr
         __syncthreads();
         carry = all;
     }
-    const float total = carry;
-    for (int t = tid; t < num; t += blockDim.x) {
-        uint32_t r[4];
-        const uint64_t ctr = offset + (uint64_t)b * num + t;
-        philox4x32((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-        const float target = u01(r[0]) * total;
-        int lo = 0, hi = F - 1;                  // first index whose cdf exceeds target (zero-weight faces are never chosen)
-        while (lo < hi) { const int mid = (lo + hi) >> 1; if (cdf[mid] > target) hi = mid; else lo = mid + 1; }
-        idx[(size_t)b * num + t] = lo;
-        float u = u01(r[1]), v = u01(r[2]);
-        if (u + v > 1.0f) { u = 1.0f - u; v = 1.0f - v; }                       // masking.py:58-60
+    return carry;
+}
+
+// draw `ctr` of stream 0: the sampled face (multinomial with replacement over the CDF) and its folded-uniform barycentrics
+__device__ __forceinline__ int face_draw(const float* cdf, int F, float total, uint64_t seed, uint64_t ctr, float bc[3]) {
+    uint32_t r[4];
+    philox4x32((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    const float target = u01(r[0]) * total;
+    int lo = 0, hi = F - 1;                      // first index whose cdf exceeds target (zero-weight faces are never chosen)
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (cdf[mid] > target) hi = mid; else lo = mid + 1; }
+    float u = u01(r[1]), v = u01(r[2]);
+    if (u + v > 1.0f) { u = 1.0f - u; v = 1.0f - v; }                           // masking.py:58-60
+    bc[0] = 1.0f - (u + v); bc[1] = u; bc[2] = v;                               // masking.py:63-68
+    return lo;
+}
+
+__global__ __launch_bounds__(1024) void sample_faces_kernel(const float* __restrict__ w, int F, int num, uint64_t seed,
+                                                            uint64_t offset, int32_t* __restrict__ idx, float* __restrict__ bary) {
+    extern __shared__ float cdf[];               // [F] inclusive prefix sums, + 32 wave totals
+    const int b = blockIdx.x;
+    const float total = face_cdf_scan(w + (size_t)b * F, F, cdf, cdf + F);
+    for (int t = threadIdx.x; t < num; t += blockDim.x) {
+        float bc[3];
+        idx[(size_t)b * num + t] = face_draw(cdf, F, total, seed, offset + (uint64_t)b * num + t, bc);
         float* o = bary + ((size_t)b * num + t) * 3;
-        o[0] = 1.0f - (u + v); o[1] = u; o[2] = v;                             // masking.py:63-68
+        o[0] = bc[0]; o[1] = bc[1]; o[2] = bc[2];
     }
 }
 
@@ -317,22 +330,11 @@ __device__ __forceinline__ void ho_ypass4(const float* h, int SW, float* o) {
     o[3] = fmaxf(fmaxf(c, v[2 * R + 3]), fmaxf(v[2 * R + 2], v[2 * R + 1]));
 }
 
-// img / rendered / masked [B][3][H][W]; hull [B or 1][H][W] with batch stride hull_bs (0 or H * W); pmask [B][H][W]; packed [B][H][W][8] split-fp16 (32 bytes a pixel)
-__global__ __launch_bounds__(HO_THREADS) void masking_handoff_kernel(const float* __restrict__ img, const float* __restrict__ rendered,
-                                                                      const float* __restrict__ hull, size_t hull_bs, const float* __restrict__ pmask,
-                                                                      int H, int W, float p_field, uint64_t seed, uint64_t field_offset,
-                                                                      uint64_t noise_offset, float* __restrict__ masked, float* __restrict__ packed) {
-    extern __shared__ __attribute__((aligned(16))) float ho_lds[];
-    const int SW1 = mp_row_stride(W, HO_R1), SW2 = mp_row_stride(W, HO_R2);
-    constexpr int NR1 = HO_ROWS + 2 * HO_R1, NR2 = HO_ROWS + 2 * HO_R2;
-    float* A1 = ho_lds;                                 // [NR1][SW1]  1 - hull, then its x maxima
-    float* A2 = ho_lds + NR1 * SW1;                     // [NR2][SW2]  patch centres, then their x maxima
-    const int tiles = (H + HO_ROWS - 1) / HO_ROWS;
-    const int b = blockIdx.x / tiles, y0 = (blockIdx.x % tiles) * HO_ROWS;
-    const size_t HW = (size_t)H * W;
-    const int tid = threadIdx.x;
+// stage 1a of the hand-off kernels: A1 [NR1][SW1] <- 1 - hull for rows [y0 - 10, y0 + HO_ROWS + 10), -inf outside the image and in the margins
+__device__ __forceinline__ void ho_stage_hull(const float* __restrict__ hsrc, float* A1, int y0, int H, int W) {
+    const int SW1 = mp_row_stride(W, HO_R1), tid = threadIdx.x;
+    constexpr int NR1 = HO_ROWS + 2 * HO_R1;
     // ---- 1a: the hull rows (eight requests in flight per lane and trip, clamped addresses + select, as maxpool_sq_lds_kernel stages them) ----
-    const float* hsrc = hull + (size_t)b * hull_bs;
     for (int base = 0; base < NR1 * SW1; base += HO_THREADS * 8) {
         float sv[8];
 #pragma unroll
@@ -348,6 +350,13 @@ __global__ __launch_bounds__(HO_THREADS) void masking_handoff_kernel(const float
             if (i < NR1 * SW1) A1[i] = sv[u];
         }
     }
+}
+
+// stage 1b: A2 [NR2][SW2] <- the patch centres of rows [y0 - 5, y0 + HO_ROWS + 5) of image `b` of the flat [.][H][W] field, -inf outside the image
+__device__ __forceinline__ void ho_stage_centres(float* A2, int b, int y0, int H, int W, float p_field, uint64_t seed, uint64_t field_offset) {
+    const int SW2 = mp_row_stride(W, HO_R2), tid = threadIdx.x;
+    constexpr int NR2 = HO_ROWS + 2 * HO_R2;
+    const size_t HW = (size_t)H * W;
     // ---- 1b: the patch-centre rows.  Cells outside the image first, then one Philox block per 4 consecutive pixels of the flat field (disjoint cells: no barrier) ----
     for (int i = tid; i < NR2 * SW2; i += HO_THREADS) {
         const int rr = i / SW2, cx = i - rr * SW2 - HO_R2, y = y0 - HO_R2 + rr;
@@ -370,6 +379,24 @@ __global__ __launch_bounds__(HO_THREADS) void masking_handoff_kernel(const float
             }
         }
     }
+}
+
+// img / rendered / masked [B][3][H][W]; hull [B or 1][H][W] with batch stride hull_bs (0 or H * W); pmask [B][H][W]; packed [B][H][W][8] split-fp16 (32 bytes a pixel)
+__global__ __launch_bounds__(HO_THREADS) void masking_handoff_kernel(const float* __restrict__ img, const float* __restrict__ rendered,
+                                                                      const float* __restrict__ hull, size_t hull_bs, const float* __restrict__ pmask,
+                                                                      int H, int W, float p_field, uint64_t seed, uint64_t field_offset,
+                                                                      uint64_t noise_offset, float* __restrict__ masked, float* __restrict__ packed) {
+    extern __shared__ __attribute__((aligned(16))) float ho_lds[];
+    const int SW1 = mp_row_stride(W, HO_R1), SW2 = mp_row_stride(W, HO_R2);
+    constexpr int NR1 = HO_ROWS + 2 * HO_R1, NR2 = HO_ROWS + 2 * HO_R2;
+    float* A1 = ho_lds;                                 // [NR1][SW1]  1 - hull, then its x maxima
+    float* A2 = ho_lds + NR1 * SW1;                     // [NR2][SW2]  patch centres, then their x maxima
+    const int tiles = (H + HO_ROWS - 1) / HO_ROWS;
+    const int b = blockIdx.x / tiles, y0 = (blockIdx.x % tiles) * HO_ROWS;
+    const size_t HW = (size_t)H * W;
+    const int tid = threadIdx.x;
+    ho_stage_hull(hull + (size_t)b * hull_bs, A1, y0, H, W);
+    ho_stage_centres(A2, b, y0, H, W, p_field, seed, field_offset);
     __syncthreads();
     // ---- 2: x passes in place ----
     ho_xpass_inplace<HO_R1>(A1, NR1, SW1, W);
@@ -599,5 +626,176 @@ extern "C" int smirk_masking_handoff(const float* img, const float* rendered_img
     smirk_prof_next(nullptr, 0.0, (double)B * H * W * (4.0 * (3 + 3 + 1 + 1 + 3) + 32.0));
     SMIRK_LAUNCH(masking_handoff_kernel, dim3((unsigned)(B * tiles)), dim3(HO_THREADS), lds, (hipStream_t)stream, img, rendered_img, hull_mask,
                  (size_t)hull_batch_stride, pmask, H, W, random_mask, seed, field_offset, noise_offset, masked_img, (float*)packed);
+    return smirk_launch_status();
+}
+
+// ---- training paths: sampled points -> generator input (include/smirk_train_handoff.h) -------------------------------------------------------
+// One sampled point on one frame: the landmark gather of v2l_kernel (flame.hip) and the quantisation of points_to_pixels_kernel, operation for operation.  The
+// gather is spelled with the roundings that unit's contraction chose, (p1 * b1, then + p0 * b0 and + p2 * b2 each as one fused multiply-add), because a pixel
+// flips if they move (tests/test_train_handoff_gpu.py compares the bits); the quantisation has no product that feeds a sum, so it contracts nowhere.
+__device__ __forceinline__ void stp_point(const float* __restrict__ vb, int i0, int i1, int i2, const float bc[3], int S, int32_t* __restrict__ xy,
+                                          long long* __restrict__ np) {
+    long long q[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float p = __fmaf_rn(vb[i2 * 3 + c], bc[2], __fmaf_rn(vb[i0 * 3 + c], bc[0], __fmul_rn(vb[i1 * 3 + c], bc[1])));
+        asm("" : "+v"(p));                                                      // a rounded fp32 value, as when it came back from memory
+        const float v = 0.5f * (1.0f + p) * (float)S;                           // masking.py:172
+        q[c] = (long long)v;                                                    // .long(): truncation toward zero
+        if (c < 2) q[c] = q[c] < 0 ? 0 : (q[c] > S - 1 ? S - 1 : q[c]);         // masking.py:174-175
+    }
+    xy[0] = (int32_t)q[0]; xy[1] = (int32_t)q[1];
+    if (np) { np[0] = q[0]; np[1] = q[1]; np[2] = q[2]; }
+}
+
+// One workgroup per source frame b: the CDF of its face weights, then per thread the draws of sample_faces_kernel (same counters), the point on the source frame
+// and on each of its Ke target frames k * B + b.  tv_dst == nullptr: no target frames (the first path transfers every point onto itself).
+__global__ __launch_bounds__(1024) void sample_transfer_points_kernel(const float* __restrict__ w, const float* __restrict__ tv_src,
+                                                                      const float* __restrict__ tv_dst, const int32_t* __restrict__ faces, int B, int Ke,
+                                                                      int V, int F, int num, int S, uint64_t seed, uint64_t offset,
+                                                                      int32_t* __restrict__ psrc, int32_t* __restrict__ pdst, long long* __restrict__ fidx,
+                                                                      float* __restrict__ bary, long long* __restrict__ np_src,
+                                                                      long long* __restrict__ np_dst) {
+    extern __shared__ float cdf[];               // [F] inclusive prefix sums, + 32 wave totals
+    const int b = blockIdx.x;
+    const float total = face_cdf_scan(w + (size_t)b * F, F, cdf, cdf + F);
+    for (int t = threadIdx.x; t < num; t += blockDim.x) {
+        float bc[3];
+        const int f = face_draw(cdf, F, total, seed, offset + (uint64_t)b * num + t, bc);
+        const size_t i = (size_t)b * num + t;
+        if (fidx) fidx[i] = f;
+        if (bary) { bary[i * 3] = bc[0]; bary[i * 3 + 1] = bc[1]; bary[i * 3 + 2] = bc[2]; }
+        const int i0 = faces[f * 3], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
+        stp_point(tv_src + (size_t)b * V * 3, i0, i1, i2, bc, S, psrc + i * 2, np_src ? np_src + i * 3 : nullptr);
+        if (tv_dst)
+            for (int k = 0; k < Ke; ++k) {
+                const size_t j = ((size_t)k * B + b) * num + t;
+                stp_point(tv_dst + ((size_t)k * B + b) * V * 3, i0, i1, i2, bc, S, pdst + j * 2, np_dst ? np_dst + j * 3 : nullptr);
+            }
+    }
+}
+
+// masking_handoff_kernel's band scheme over the Ke * B output frames of a training path.  Output frame kb reads img and hull of source frame kb % B, its own
+// rendering and its own targets; the pixel transfer happens in LDS:
+//   1  stage 1 - hull and the patch centres as there (the field is drawn per OUTPUT frame), and a [HO_ROWS][W] winner band set to -1
+//   2  the x passes in place; meanwhile the frame's N targets are scanned and every one that lands in the band raises its pixel's cell to its point index with an
+//      LDS atomicMax: the highest index wins, as transfer_winner_kernel decides over the whole image.  Both touch disjoint LDS, so they share one barrier interval
+//   3  the y passes; the extra value of a pixel is the source pixel of its winner (else 0); the rendered mask under `rule`; composition, masked and packed
+// LDS: ho_lds_bytes(W) + HO_ROWS * W * 4 = 75,584 bytes at W = 224: two workgroups per CU.
+static inline size_t tho_lds_bytes(int W) { return ho_lds_bytes(W) + (size_t)HO_ROWS * W * sizeof(int); }
+
+__global__ __launch_bounds__(HO_THREADS) void train_masking_handoff_kernel(const float* __restrict__ img, const float* __restrict__ rendered,
+                                                                            const float* __restrict__ hull, size_t hull_bs, const int2* __restrict__ psrc,
+                                                                            const int2* __restrict__ pdst, int B, int N, int H, int W, int rule, float p_field,
+                                                                            uint64_t seed, uint64_t field_offset, uint64_t noise_offset,
+                                                                            float* __restrict__ masked, float* __restrict__ packed) {
+    extern __shared__ __attribute__((aligned(16))) float ho_lds[];
+    const int SW1 = mp_row_stride(W, HO_R1), SW2 = mp_row_stride(W, HO_R2);
+    constexpr int NR1 = HO_ROWS + 2 * HO_R1, NR2 = HO_ROWS + 2 * HO_R2;
+    float* A1 = ho_lds;                                 // [NR1][SW1]  1 - hull, then its x maxima
+    float* A2 = ho_lds + NR1 * SW1;                     // [NR2][SW2]  patch centres, then their x maxima
+    int* win = (int*)(A2 + NR2 * SW2);                  // [HO_ROWS][W] highest point index that lands on the pixel, -1: none
+    const int tiles = (H + HO_ROWS - 1) / HO_ROWS;
+    const int kb = blockIdx.x / tiles, y0 = (blockIdx.x % tiles) * HO_ROWS, bs = kb % B;
+    const size_t HW = (size_t)H * W;
+    const int tid = threadIdx.x;
+    ho_stage_hull(hull + (size_t)bs * hull_bs, A1, y0, H, W);
+    ho_stage_centres(A2, kb, y0, H, W, p_field, seed, field_offset);
+    for (int i = tid; i < HO_ROWS * W; i += HO_THREADS) win[i] = -1;
+    __syncthreads();
+    // ---- 2: the transfer's winners, and the x passes in place ----
+    const int2* pd = pdst + (size_t)kb * N;
+    for (int l = tid; l < N; l += HO_THREADS) {
+        const int2 t = pd[l];
+        const int ry = t.y - y0;
+        if (t.x >= 0 && t.x < W && t.y >= 0 && t.y < H && ry >= 0 && ry < HO_ROWS) atomicMax(&win[ry * W + t.x], l);
+    }
+    ho_xpass_inplace<HO_R1>(A1, NR1, SW1, W);
+    ho_xpass_inplace<HO_R2>(A2, NR2, SW2, W);
+    __syncthreads();
+    // ---- 3: y passes, transfer, composition, both stores ----
+    const float* ib = img + (size_t)bs * 3 * HW;
+    const float* rb = rendered + (size_t)kb * 3 * HW;
+    const int2* ps = psrc + (size_t)bs * N;
+    float* mb = masked + (size_t)kb * 3 * HW;
+    float* pk = packed + (size_t)kb * HW * 8;
+    for (int i = tid; i < (HO_ROWS / 4) * W; i += HO_THREADS) {
+        const int q = i / W, x = i - q * W;
+        float er[4], dl[4];
+        ho_ypass4<HO_R1>(A1 + (q * 4) * SW1 + x, SW1, er);        // staged row q*4 + k = image row y0 + q*4 - R + k
+        ho_ypass4<HO_R2>(A2 + (q * 4) * SW2 + x, SW2, dl);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int y = y0 + q * 4 + k;
+            if (y >= H) continue;
+            const size_t pix = (size_t)y * W + x;
+            float mask_d = 1.0f - er[k], keep = 1.0f - dl[k];     // what the two max pools stored: 1 - maxpool(1 - mask), 1 - maxpool(centres)
+            asm("" : "+v"(mask_d));                               // rounded fp32 values, as when they came back from memory
+            asm("" : "+v"(keep));
+            const int l = win[(q * 4 + k) * W + x];
+            size_t spix = 0;
+            bool has = false;
+            if (l >= 0) {
+                const int2 s = ps[l];
+                has = s.x >= 0 && s.x < W && s.y >= 0 && s.y < H;
+                if (has) spix = (size_t)s.y * W + s.x;
+            }
+            float v[8];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c] = rb[c * HW + pix];
+            const bool covered = rule == SMIRK_RENDERED_RULE_POSITIVE ? (v[0] > 0.0f && v[1] > 0.0f && v[2] > 0.0f)      // (r > 0).all(1)
+                                                                      : !(v[0] == 0.0f && v[1] == 0.0f && v[2] == 0.0f); // 1 - (r == 0).all(1)
+            float rm = covered ? 1.0f : 0.0f;
+            asm("" : "+v"(rm));
+            const float m = mask_d * (1.0f - rm);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float e = has ? ib[c * HW + spix] : 0.0f;   // transfer_gather_kernel
+                const float o = masking_compose1(ib[c * HW + pix], m, e, nullptr, 1, seed, noise_offset + ((size_t)kb * 3 + c) * HW + pix, true, keep);
+                mb[c * HW + pix] = o;
+                v[3 + c] = o;
+            }
+            v[6] = 0.f; v[7] = 0.f;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) smirk_range_audit1(v[c]);  // the network INPUT, as pack_split_kernel audits it
+            half8 hi, lo;
+            split8(v, hi, lo);
+            *(half8*)(pk + pix * 8) = hi;
+            *(half8*)(pk + pix * 8 + 4) = lo;
+        }
+    }
+}
+
+extern "C" int smirk_train_handoff_abi_version(void) { return SMIRK_TRAIN_HANDOFF_ABI_VERSION; }
+
+extern "C" int smirk_sample_transfer_points(const float* weights, const float* tv_src, const float* tv_dst, const int32_t* faces, int B, int Ke, int V, int F,
+                                            int num, int image_size, uint64_t seed, uint64_t offset, int32_t* points_src, int32_t* points_dst,
+                                            int64_t* faces_idx, float* bary, int64_t* npoints_src, int64_t* npoints_dst, void* stream) {
+    if (!weights || !tv_src || !faces || !points_src) return SMIRK_ERR_BAD_ARG;
+    if (B <= 0 || Ke <= 0 || V <= 0 || F <= 0 || num <= 0 || image_size <= 0 || F > 38000 || image_size > 32768) return SMIRK_ERR_BAD_ARG;
+    if (tv_dst ? !points_dst : (Ke != 1 || points_dst || npoints_dst)) return SMIRK_ERR_BAD_ARG;
+    SMIRK_LAUNCH(sample_transfer_points_kernel, dim3(B), dim3(1024), (size_t)(F + 32) * 4, (hipStream_t)stream, weights, tv_src, tv_dst, faces, B, Ke, V, F, num,
+                 image_size, seed, offset, points_src, points_dst, (long long*)faces_idx, bary, (long long*)npoints_src, (long long*)npoints_dst);
+    return smirk_launch_status();
+}
+
+extern "C" int smirk_train_masking_handoff(const float* img, const float* rendered_img, const float* hull_mask, long long hull_batch_stride,
+                                           const int32_t* points_src, const int32_t* points_dst, int B, int Ke, int N, int H, int W, int rendered_rule,
+                                           float random_mask, uint64_t seed, uint64_t field_offset, uint64_t noise_offset, float* masked_img, void* packed,
+                                           void* stream) {
+    if (!img || !rendered_img || !hull_mask || !points_src || !points_dst || !masked_img || !packed) return SMIRK_ERR_BAD_ARG;
+    if (B <= 0 || Ke <= 0 || N <= 0 || H <= 0 || W <= 0) return SMIRK_ERR_BAD_ARG;
+    if (hull_batch_stride != 0 && hull_batch_stride != (long long)H * W) return SMIRK_ERR_BAD_ARG;
+    if (!(random_mask > 0.0f)) return SMIRK_ERR_BAD_ARG;                                            // masking() draws no field then: that path keeps its launches
+    if (rendered_rule != SMIRK_RENDERED_RULE_NONZERO && rendered_rule != SMIRK_RENDERED_RULE_POSITIVE) return SMIRK_ERR_BAD_ARG;
+    const size_t lds = tho_lds_bytes(W);
+    const long long tiles = (H + HO_ROWS - 1) / HO_ROWS, frames = (long long)B * Ke;
+    // two workgroups per CU need at most 80 KB each; the flat field index of a pixel is taken relative to its frame in 32 bits
+    if (lds > 80 * 1024 || frames * tiles >= 0x7fffffffll || (long long)H * W >= 0x7fffffffll) return SMIRK_ERR_UNSUPPORTED;
+    if (smirk_raise_dynamic_lds((const void*)train_masking_handoff_kernel, 80 * 1024) != SMIRK_OK) return SMIRK_ERR_UNSUPPORTED;
+    smirk_prof_next(nullptr, 0.0, (double)frames * H * W * (4.0 * (3 + 3 + 1 + 3) + 32.0));
+    SMIRK_LAUNCH(train_masking_handoff_kernel, dim3((unsigned)(frames * tiles)), dim3(HO_THREADS), lds, (hipStream_t)stream, img, rendered_img, hull_mask,
+                 (size_t)hull_batch_stride, (const int2*)points_src, (const int2*)points_dst, B, N, H, W, rendered_rule, random_mask, seed, field_offset,
+                 noise_offset, masked_img, (float*)packed);
     return smirk_launch_status();
 }

@@ -34,6 +34,10 @@
 //                                   masking_handoff_kernel + smirk_generator_forward_packed; same output bits (tests/test_masking_handoff_gpu.py,
 //                                   tests/test_generator_packed_gpu.py).  The choice between the two is made where the tensors are allocated, in Python, so the
 //                                   variable is read there and is not a member of the enum below.
+// SMIRK_DISABLE_TRAIN_HANDOFF       set (any value): masking.train_masked_image_packed, and with it cycle.render_second_path / second_path_packed and
+//                                   first_path.forward_first_path, keeps the separate utilities (two point samplings, transfer_pixels, rendered mask, masking,
+//                                   the generator's own cat + pack) instead of sample_transfer_points_kernel + train_masking_handoff_kernel +
+//                                   SmirkGenerator.forward_pair_packed; same output bits (tests/test_train_handoff_gpu.py).  Read in Python, like the one above.
 #pragma once
 
 #define SMIRK_WGRAD_F16_DEFAULT 2

@@ -10,7 +10,8 @@ exactly that sequence:
     with no_grad:   FLAME(encoder_output), Renderer(...)                       smirk_trainer.py:247-249   (sampling of the source points)
                     FLAME(augmented params), Renderer(...)  -> rendered        smirk_trainer.py:252-254
                     mesh_based_mask_uniform_faces x2, transfer_pixels, mask    smirk_trainer.py:262-289
-    masking(...)    -> masked image                                            smirk_trainer.py:290-291
+    masking(...)    -> masked image                                            smirk_trainer.py:290-291   (:262-291 as masking.train_masked_image_packed: two
+                                                                               launches behind the face weights, Ke by index, same bits - DESIGN.md 33)
     generator(cat[rendered, masked])          TRAIN mode (batch-statistic BN)  smirk_trainer.py:293
     encoder(reconstructed)                    TRAIN mode                       smirk_trainer.py:297
     FLAME / Renderer of the re-encoded parameters (visualisation only)         smirk_trainer.py:299-300
@@ -41,9 +42,8 @@ def cycle_loss(recon_feats, flame_feats, use_eyelids=True, generator_frozen=Fals
     return loss
 
 
-def render_second_path(flame, renderer, encoder_output, flame_feats, img, masks, face_probabilities, masking_utils, mask_ratio=0.01,
-                       mask_dilation_radius=10, Ke=1):
-    """smirk_trainer.py:245-291: everything between the augmented parameters and the generator's input.  Returns (rendered, masked)."""
+def _render_second_path(flame, renderer, encoder_output, flame_feats, img, masks, face_probabilities, masking_utils, mask_ratio, mask_dilation_radius, Ke):
+    """-> (rendered, masked, packed): `packed` is the generator's packed network input where masking_utils.train_masked_image_packed wrote it, else None"""
     with torch.no_grad():
         flame_output = flame.forward(encoder_output)
         rendered_output = renderer.forward(flame_output['vertices'], encoder_output['cam'])
@@ -52,6 +52,14 @@ def render_second_path(flame, renderer, encoder_output, flame_feats, img, masks,
         cam = encoder_output['cam'] if Ke == 1 else encoder_output['cam'].repeat(Ke, 1)
         renderer_output_2nd = renderer.forward(flame_output_2nd['vertices'], cam)
         rendered_2nd = renderer_output_2nd['rendered_img'].detach()
+        fused = getattr(masking_utils, "train_masked_image_packed", None)
+        if fused is not None:
+            # both point samplings, transfer_pixels, the rendered mask, masking and the generator's pack: two launches after the face weights where the fused
+            # form serves the call, the separate utilities under the same draws where it does not (`packed` is None then).  Nothing is repeated Ke times.
+            masked_2nd, packed, _ = fused(img, masks, rendered_2nd, flame_output['transformed_vertices'], flame.faces_tensor, face_probabilities,
+                                          trans_verts_dst=renderer_output_2nd['transformed_vertices'], Ke=Ke, mask_ratio=mask_ratio,
+                                          mask_dilation_radius=mask_dilation_radius, rendered_rule="positive", random_mask=0.005, image_size=224)
+            return rendered_2nd, masked_2nd, packed
         points1, coords = masking_utils.mesh_based_mask_uniform_faces(flame_output['transformed_vertices'], flame_faces=flame.faces_tensor,
                                                                       face_probabilities=face_probabilities, mask_ratio=mask_ratio)
         coords['sampled_faces_indices'] = coords['sampled_faces_indices'].repeat(Ke, 1)
@@ -62,7 +70,13 @@ def render_second_path(flame, renderer, encoder_output, flame_feats, img, masks,
         rendered_mask = (rendered_2nd > 0).all(dim=1, keepdim=True).float()
     masked_2nd = masking_utils.masking(img.repeat(Ke, 1, 1, 1), masks.repeat(Ke, 1, 1, 1), extra_points, mask_dilation_radius, rendered_mask=rendered_mask,
                                        extra_noise=True, random_mask=0.005)
-    return rendered_2nd, masked_2nd
+    return rendered_2nd, masked_2nd, None
+
+
+def render_second_path(flame, renderer, encoder_output, flame_feats, img, masks, face_probabilities, masking_utils, mask_ratio=0.01,
+                       mask_dilation_radius=10, Ke=1):
+    """smirk_trainer.py:245-291: everything between the augmented parameters and the generator's input.  Returns (rendered, masked)."""
+    return _render_second_path(flame, renderer, encoder_output, flame_feats, img, masks, face_probabilities, masking_utils, mask_ratio, mask_dilation_radius, Ke)[:2]
 
 
 def second_path(flame, renderer, encoder_output, bank, img, masks, face_probabilities, masking_utils, Ke=1, num_expression=50, use_eyelids=True,
@@ -76,9 +90,25 @@ def second_path(flame, renderer, encoder_output, bank, img, masks, face_probabil
     return flame_feats, rendered, masked
 
 
-def cycle_forward(generator, encoder, rendered, masked, flame_feats, freeze_generator=False, use_eyelids=True):
-    """smirk_trainer.py:293-313: generator -> encoder -> cycle loss.  Returns (loss, reconstructed image, re-encoded parameters)."""
-    recon = generator(torch.cat([rendered, masked], dim=1).detach())
+def second_path_packed(flame, renderer, encoder_output, bank, img, masks, face_probabilities, masking_utils, Ke=1, num_expression=50, use_eyelids=True,
+                       mask_ratio=0.01, mask_dilation_radius=10, _rng_stream=None):
+    """`second_path` for a caller that hands the result to `cycle_forward(..., packed=packed)`: returns (flame_feats, rendered, masked, packed), where `packed`
+    [Ke*B,H,W,8] is the generator's split-fp16 network input of cat(rendered, masked), written beside `masked` by the same launch
+    (masking.train_masked_image_packed), or None where that launch does not serve the call.  The other three are `second_path`'s, bit for bit."""
+    from .augment import augment_flame_params
+    flame_feats = augment_flame_params(encoder_output, bank, Ke=Ke, num_expression=num_expression, use_eyelids=use_eyelids, _rng_stream=_rng_stream)
+    return (flame_feats,) + _render_second_path(flame, renderer, encoder_output, flame_feats, img, masks, face_probabilities, masking_utils, mask_ratio,
+                                                mask_dilation_radius, Ke)
+
+
+def cycle_forward(generator, encoder, rendered, masked, flame_feats, freeze_generator=False, use_eyelids=True, packed=None):
+    """smirk_trainer.py:293-313: generator -> encoder -> cycle loss.  Returns (loss, reconstructed image, re-encoded parameters).  `packed`: the generator's
+    packed network input of cat(rendered, masked) from `second_path_packed`; where the generator takes it (SmirkGenerator.accepts_pair_packed) the
+    concatenation and the pack launch are skipped, with the same bits."""
+    if packed is not None and getattr(generator, "accepts_pair_packed", lambda r: False)(rendered):
+        recon = generator.forward_pair_packed(rendered.detach(), packed)
+    else:
+        recon = generator(torch.cat([rendered, masked], dim=1).detach())
     if freeze_generator:
         recon = recon.detach()
     feats = encoder(recon)

@@ -7,11 +7,10 @@ The trainer itself — dataset, logging, optimiser, the `.cpu()` copies of its v
     base_encoder(batch['img'])  (no_grad, optional)             -> base_output           smirk_trainer.py:40-41, 64-68
     FLAME(encoder_output)                                       -> vertices, landmarks   smirk_trainer.py:43
     Renderer(vertices, cam, landmarks_fan=, landmarks_mp=)      -> rendered, landmarks   smirk_trainer.py:46-49
-    masking.rendered_mask_of(rendered)                          -> rendered_mask         smirk_trainer.py:79
-    masking.mesh_based_mask_uniform_faces(transformed_vertices) -> npoints               smirk_trainer.py:83-86
-    masking.transfer_pixels(img, npoints, npoints)              -> extra_points          smirk_trainer.py:89
-    masking.masking(img, masks, extra_points, radius, rendered_mask)  -> masked_img      smirk_trainer.py:92
-    generator(cat[rendered, masked_img])                        -> reconstructed_img     smirk_trainer.py:94
+    masking.train_masked_image_packed(...)                      -> masked_img, packed    smirk_trainer.py:79-92: rendered_mask_of, mesh_based_mask_uniform_faces,
+                                                                                         transfer_pixels(img, npoints, npoints) and masking() as two launches
+                                                                                         behind the face weights, same bits
+    generator.forward_pair_packed(rendered, packed)             -> reconstructed_img     smirk_trainer.py:94: generator(cat[rendered, masked_img]) from the packed input
     FirstPathLoss (smirk_amd.losses)                            -> loss, terms, loss_img smirk_trainer.py:56-72, 97-101, 134-154
     perceptual / emotion / MICA terms (:104-131)                -> `extra`: added by FirstPathLoss with their weights.  The perceptual term is
                                                                    smirk_amd.VGGPerceptualLoss, the MICA term (pre-training stage, :128-131) is
@@ -45,13 +44,16 @@ def forward_first_path(encoder, flame, renderer, generator, batch, face_probabil
                transformed_vertices=renderer_output['transformed_vertices'], landmarks_fan=renderer_output['landmarks_fan'],
                landmarks_mp=renderer_output['landmarks_mp'])
     if enable_fuse_generator:
-        rendered_mask = masking_utils.rendered_mask_of(rendered_img)
-        npoints, _ = masking_utils.mesh_based_mask_uniform_faces(renderer_output['transformed_vertices'], flame_faces=flame.faces_tensor,
-                                                                 face_probabilities=face_probabilities, mask_ratio=mask_ratio, _rng_stream=_rng_stream)
-        extra_points = masking_utils.transfer_pixels(img, npoints, npoints)
-        masked_img = masking_utils.masking(img, batch['mask'], extra_points, mask_dilation_radius, rendered_mask=rendered_mask, _rng_stream=_rng_stream)
+        # rendered mask, point sampling, transfer_pixels(img, npoints, npoints), masking and the generator's pack: two launches after the face weights where
+        # masking.train_masked_image_packed serves the call, the separate utilities under the same draws where it does not (`packed` is None then)
+        masked_img, packed, _ = masking_utils.train_masked_image_packed(img, batch['mask'], rendered_img, renderer_output['transformed_vertices'], flame.faces_tensor,
+                                                                        face_probabilities, mask_ratio=mask_ratio, mask_dilation_radius=mask_dilation_radius,
+                                                                        rendered_rule="nonzero", random_mask=0.01, rng=_rng_stream, image_size=224)
         out['masked_1st_path'] = masked_img
-        out['reconstructed_img'] = generator(torch.cat([rendered_img, masked_img], dim=1))
+        if packed is not None and getattr(generator, "accepts_pair_packed", lambda r: False)(rendered_img):
+            out['reconstructed_img'] = generator.forward_pair_packed(rendered_img, packed)
+        else:
+            out['reconstructed_img'] = generator(torch.cat([rendered_img, masked_img], dim=1))
     return out
 
 

@@ -324,198 +324,238 @@ class GeneratorTrainFunction(torch.autograd.Function):
     def forward(ctx, module, x, *params):
         x = L.as_f32c(x.detach())
         B, Cx, H, W = x.shape
-        if Cx != module.in_channels or H % 16 or W % 16:
-            raise L.SmirkHipError("SmirkGenerator: expected [B, in_channels, H, W] with H, W multiples of 16")
-        if module.features % 8 or module.in_channels > 8:
-            raise L.SmirkHipError("training runs in the split-fp16 mode: init_features % 8 == 0 and in_channels <= 8")
-        ctx.arith = getattr(module, "train_arith", "f16x3")
-        ops = _Ops(x.device, eval_bn=not module.training, arith=ctx.arith)
-        lib, st, f = ops.lib, ops.st, module.features
-        ctx.eval_bn = not module.training
-        plan = getattr(module, "_pack_plan", None)
-        if plan is None or not plan.valid_for(params):                    # first forward (or the parameters were re-allocated): record
-            plan = PackPlan()
-            object.__setattr__(module, "_pack_plan", plan)
-        else:
-            plan.run(ops)                                                 # every conv weight of the network: one launch
-        ops.plan = plan
-        tape = []                                                         # records consumed in reverse by backward()
+        _check_train_input(module, Cx, H, W)
         xin = torch.empty(B, H, W, 8, device=x.device)
-        L.check(lib.smirk_pack_generator_input_split16(L.ptr(x), Cx, None, 0, L.ptr(xin), B, H, W, st))
-
-        def block(seq, tag, x0, x1, h, w, c):
-            m = dict(seq.named_children())
-            c1, n1, c2, n2 = m[tag + "conv1"], m[tag + "norm1"], m[tag + "conv2"], m[tag + "norm2"]
-            c0 = x0.shape[-1]
-            if x1 is None:
-                wf1, wd1a = ops.pack(c1.weight, cin_pad=c0)
-                wd1b = None
-            else:                                                          # decoder: forward weight over cat(up, skip), one data-gradient weight per source
-                wf1, _ = ops.pack(c1.weight, dgrad=False)
-                wd1a = ops.pack(c1.weight, 0, c0, fwd=False)[1]
-                wd1b = ops.pack(c1.weight, c0, x1.shape[-1], fwd=False)[1]
-            z1, st1 = ops.conv_stats(x0, x1, wf1, B, h, w, c)
-            y1, mu1, iv1 = ops.bn_forward(z1, n1, True, stats=st1)
-            wf2, wd2 = ops.pack(c2.weight)
-            z2, st2 = ops.conv_stats(y1, None, wf2, B, h, w, c)
-            y2, mu2, iv2 = ops.bn_forward(z2, n2, True, stats=st2)
-            tape.append(("block", (c1, n1, c2, n2), (x0, x1, z1, mu1, iv1, y1, z2, mu2, iv2, wd1a, wd1b, wd2), (h, w, c)))
-            return y2
-
-        def pool(t, h, w, c):
-            o = torch.empty(B, h // 2, w // 2, c, device=t.device)
-            L.check(lib.smirk_maxpool2x2_split16(L.ptr(t), L.ptr(o), B, h, w, c, st))
-            tape.append(("pool", None, (t,), (h, w, c)))
-            return o
-
-        e1 = block(module.encoder1, "enc1", xin, None, H, W, f)
-        e2 = block(module.encoder2, "enc2", pool(e1, H, W, f), None, H // 2, W // 2, 2 * f)
-        e3 = block(module.encoder3, "enc3", pool(e2, H // 2, W // 2, 2 * f), None, H // 4, W // 4, 4 * f)
-        e4 = block(module.encoder4, "enc4", pool(e3, H // 4, W // 4, 4 * f), None, H // 8, W // 8, 8 * f)
-        h16, w16, c16 = H // 16, W // 16, 16 * f
-        b = block(module.bottleneck, "bottleneck", pool(e4, H // 8, W // 8, 8 * f), None, h16, w16, c16)
-        for rb in module.resnet_blocks:
-            cb = rb.conv_block
-            wfa, wda = ops.pack(cb[1].weight)
-            za, sta = ops.conv_stats(b, None, wfa, B, h16, w16, c16, reflect=True)
-            ya, mua, iva = ops.bn_forward(za, cb[2], True, stats=sta)
-            wfb, wdb = ops.pack(cb[5].weight)
-            zb, stb = ops.conv_stats(ya, None, wfb, B, h16, w16, c16, reflect=True)
-            nb, mub, ivb = ops.bn_forward(zb, cb[6], False, residual=b, stats=stb)
-            tape.append(("res", (cb[1], cb[2], cb[5], cb[6]), (b, za, mua, iva, ya, zb, mub, ivb, wda, wdb), (h16, w16, c16)))
-            b = nb
-        d = b
-        for lvl, skip, div, c in ((4, e4, 16, 8 * f), (3, e3, 8, 4 * f), (2, e2, 4, 2 * f), (1, e1, 2, f)):
-            up = getattr(module, f"upconv{lvl}")
-            wup, wupd = plan.request_special(ops, up.weight, L.PACK_CONVT2X2)   # [Cin, Cout, 2, 2] -> forward 1x1 image, data-gradient image (same launch as every other weight)
-            u = ops.conv(d, None, wup, B, H // div, W // div, c, k=1, convt=True, shift=up.bias.detach().float().contiguous())
-            tape.append(("up", (up,), (d, wupd), (H // div, W // div, 2 * c, c)))
-            d = block(getattr(module, f"decoder{lvl}"), f"dec{lvl}", u, skip, 2 * H // div, 2 * W // div, c)
-        wf = module.conv.weight.detach().float().reshape(module.out_channels, f).contiguous()
-        bf = module.conv.bias.detach().float().contiguous()
-        y = torch.empty(B, module.out_channels, H, W, device=x.device)
-        L.check(lib.smirk_conv1x1_sigmoid_nchw_split16(L.ptr(d), L.ptr(wf), L.ptr(bf), L.ptr(y), B, H, W, f, module.out_channels, st))
-        if not plan.sealed:
-            plan.seal(params, x.device)
-        ctx.plan, (ctx.plan_generation, ctx.plan_versions) = plan, plan.stamp(params)
-        ctx.rm_saved = ops.rm_saved
-        ctx.module, ctx.tape, ctx.final = module, tape, (d, wf, y)
-        ctx.shape = (B, Cx, H, W)
-        return y
+        L.check(L.lib().smirk_pack_generator_input_split16(L.ptr(x), Cx, None, 0, L.ptr(xin), B, H, W, L.stream_ptr()))
+        ctx.param_at = 2
+        return _train_forward(ctx, module, xin, (B, Cx, H, W), params)
 
     @staticmethod
     def backward(ctx, gy):
-        if ctx.tape is None:
-            raise L.second_backward("GeneratorTrainFunction", "raw convolution outputs")
-        module, tape, (d1, wf, y) = ctx.module, ctx.tape, ctx.final
-        B, Cx, H, W = ctx.shape
-        f = module.features
-        ctx.plan.check_tape(ctx.plan_generation, ctx.plan_versions)
-        ops = _Ops(y.device, eval_bn=ctx.eval_bn, arith=ctx.arith)
-        ops.rm_saved = ctx.rm_saved
-        lib, st = ops.lib, ops.st
-        grads = {}                                                        # id(parameter) -> gradient in the parameter's layout
-        # which parameters wanted a gradient WHEN THE FORWARD RAN (smirk_trainer.py:108-113 flips requires_grad off for the eval-mode forward and back on
-        # before backward): a frozen generator pays for data gradients only; in eval mode BatchNorm's affine gradients are not computed at all
-        wanted = {id(p) for p, n in zip(module.parameters(), ctx.needs_input_grad[2:]) if n}
-        if ctx.eval_bn and any(id(bn_p) in wanted for m_ in module.modules() if isinstance(m_, torch.nn.BatchNorm2d) for bn_p in m_.parameters()):
-            raise L.SmirkHipError("eval-mode SmirkGenerator inside autograd: parameter gradients are not implemented (freeze the generator as "
-                                  "smirk_trainer.py:108-113 does, or call .train())")
-        need = lambda p: id(p) in wanted
-        want_dx = bool(ctx.needs_input_grad[1])
-        gy = L.as_f32c(gy)
-        # ---- final 1x1 conv + sigmoid ------------------------------------------------------------------------------------------------------
-        dd = torch.empty_like(d1)
-        dl8 = torch.empty(B, H, W, 8, device=y.device)
-        L.check(lib.smirk_conv1x1_sigmoid_backward_split16(L.ptr(gy), L.ptr(y), L.ptr(wf), L.ptr(dd), L.ptr(dl8), B, H, W, f, module.out_channels, st))
-        if need(module.conv.weight):
-            grads[id(module.conv.weight)] = ops.wgrad(dl8, d1, B, H, W, 8, f, 1)[:module.out_channels].reshape(module.out_channels, f, 1, 1)
-        if need(module.conv.bias):
-            grads[id(module.conv.bias)] = ops.colsum(dl8)[:module.out_channels].contiguous()
+        g, param_grads = _train_backward(ctx, gy)
+        Cx = ctx.shape[1]
+        dx = split16_to_float(g)[..., :Cx].permute(0, 3, 1, 2).contiguous() if g is not None else None
+        return (None, dx) + param_grads
 
-        def block_backward(rec, g):
-            """g = dL/d(block output) -> (dL/d x0, dL/d x1 or None)"""
-            _, (c1, n1, c2, n2), (x0, x1, z1, mu1, iv1, y1, z2, mu2, iv2, wd1a, wd1b, wd2), (h, w, c) = rec
-            dz2, dg2, db2 = ops.bn_backward(z2, g, n2, mu2, iv2, True)
-            if dg2 is not None:
-                grads[id(n2.weight)], grads[id(n2.bias)] = dg2, db2
-            if need(c2.weight):
-                grads[id(c2.weight)] = ops.wgrad_param(dz2, y1, B, h, w, c, c, 3, _grad_like(c2.weight))
-            dy1 = ops.conv(dz2, None, wd2, B, h, w, c)
-            dz1, dg1, db1 = ops.bn_backward(z1, dy1, n1, mu1, iv1, True)
-            if dg1 is not None:
-                grads[id(n1.weight)], grads[id(n1.bias)] = dg1, db1
-            c0 = x0.shape[-1]
-            if x1 is None:
-                if need(c1.weight):                                       # (the network input is padded 6 -> 8 channels: the two padded ones are dropped)
-                    if c1.weight.shape[1] > c0:
-                        raise L.SmirkHipError(f"conv expects {c1.weight.shape[1]} input channels, its source carries {c0}")
-                    grads[id(c1.weight)] = ops.wgrad_param(dz1, x0, B, h, w, c, c0, 3, _grad_like(c1.weight), cin_real=c1.weight.shape[1])
-                if rec is tape[0] and not want_dx:                        # the network input needs no gradient (cycle path: it is detached)
-                    return None, None
-                return ops.conv(dz1, None, wd1a, B, h, w, c0), None
-            cc1 = x1.shape[-1]
-            if need(c1.weight):                                           # torch.cat((up, skip), 1): channels of source 0 first, both into one tensor
-                if c0 + cc1 != c1.weight.shape[1]:                        # every channel of the parameter must be written by one of the two calls
-                    raise L.SmirkHipError(f"decoder conv expects {c1.weight.shape[1]} input channels, its two sources carry {c0} + {cc1}")
-                gw = _grad_like(c1.weight)
-                ops.wgrad_param(dz1, x0, B, h, w, c, c0, 3, gw, cin_off=0)
-                ops.wgrad_param(dz1, x1, B, h, w, c, cc1, 3, gw, cin_off=c0)
-                grads[id(c1.weight)] = gw
-            return ops.conv(dz1, None, wd1a, B, h, w, c0), ops.conv(dz1, None, wd1b, B, h, w, cc1)
 
-        g = dd
-        skip_grad = {}
-        i = len(tape) - 1
-        lvl = 1
-        while i >= 0:
-            rec = tape[i]
-            kind = rec[0]
-            if kind == "block":
-                g0, g1 = block_backward(rec, g)
-                if g1 is not None:                                         # decoder block: x0 = up-sampled tensor, x1 = the encoder's skip tensor
-                    skip_grad[lvl] = g1
-                    lvl += 1
-                g = g0
-            elif kind == "up":
-                (up,), (xin_, wd), (h, w, cin, cout) = rec[1], rec[2], rec[3]
-                s2d = torch.empty(B, h, w, 4 * cout, device=y.device)
-                L.check(lib.smirk_space_to_depth2_split16(L.ptr(g), L.ptr(s2d), B, h, w, cout, st))
-                if need(up.bias):
-                    grads[id(up.bias)] = ops.colsum(g)
-                if need(up.weight):                                        # packed [Cin][(dy,dx,co)] -> the parameter's [Cin][Cout][2][2] in the reduction itself
-                    grads[id(up.weight)] = ops.wgrad_param(xin_, s2d, B, h, w, cin, 4 * cout, 1, _grad_like(up.weight), layout=2)
-                g = ops.conv(s2d, None, wd, B, h, w, cin, k=1)
-            elif kind == "res":
-                _, (ca, na, cbv, nbv), (bin_, za, mua, iva, ya, zb, mub, ivb, wda, wdb), (h, w, c) = rec
-                dzb, dgb, dbb = ops.bn_backward(zb, g, nbv, mub, ivb, False)
-                if dgb is not None:
-                    grads[id(nbv.weight)], grads[id(nbv.bias)] = dgb, dbb
-                if need(cbv.weight):
-                    grads[id(cbv.weight)] = ops.wgrad_param(dzb, ya, B, h, w, c, c, 3, _grad_like(cbv.weight), reflect=True)
-                dpad = ops.conv(dzb, None, wdb, B, h, w, c, pad=2, out_hw=(h + 2, w + 2))
-                dya = torch.empty_like(ya)
-                L.check(lib.smirk_reflect_pad1_backward_split16(L.ptr(dpad), None, L.ptr(dya), B, h, w, c, st))
-                dza, dga, dba = ops.bn_backward(za, dya, na, mua, iva, True)
-                if dga is not None:
-                    grads[id(na.weight)], grads[id(na.bias)] = dga, dba
-                if need(ca.weight):
-                    grads[id(ca.weight)] = ops.wgrad_param(dza, bin_, B, h, w, c, c, 3, _grad_like(ca.weight), reflect=True)
-                dpad = ops.conv(dza, None, wda, B, h, w, c, pad=2, out_hw=(h + 2, w + 2))
-                gin = torch.empty_like(bin_)
-                L.check(lib.smirk_reflect_pad1_backward_split16(L.ptr(dpad), L.ptr(g), L.ptr(gin), B, h, w, c, st))     # + the identity branch
-                g = gin
-            elif kind == "pool":
-                (t,), (h, w, c) = rec[2], rec[3]
-                level = {f: 1, 2 * f: 2, 4 * f: 3, 8 * f: 4}[c]
-                gx = torch.empty_like(t)
-                L.check(lib.smirk_maxpool2x2_backward_split16(L.ptr(t), L.ptr(g), L.ptr(skip_grad.get(level), allow_none=True), L.ptr(gx), B, h, w, c, st))
-                g = gx
-            i -= 1
-        dx = split16_to_float(g)[..., :Cx].permute(0, 3, 1, 2).contiguous() if (want_dx and g is not None) else None
-        ctx.tape = ctx.final = None
-        out = [None, dx]
-        for p in module.parameters():
-            gp = grads.get(id(p))
-            out.append(None if gp is None else gp.reshape(p.shape).to(p.dtype))
-        return tuple(out)
+class GeneratorTrainPackedFunction(torch.autograd.Function):
+    """GeneratorTrainFunction from the packed split-fp16 network input [B,H,W,8] of cat(rendered, masked) that masking.train_masked_image_packed wrote: no
+    torch.cat and no pack launch, the same tape from there on.  Differentiable w.r.t. `rendered` (channels 0-2 of the input gradient) and every parameter;
+    nothing flows into `packed`, which must stay untouched until the backward has run (the first convolution's weight gradient reads it)."""
+
+    @staticmethod
+    def forward(ctx, module, rendered, packed, *params):
+        B, H, W, _ = packed.shape
+        _check_train_input(module, 6, H, W)
+        if tuple(rendered.shape) != (B, 3, H, W) or packed.shape[3] != 8:
+            raise L.SmirkHipError("SmirkGenerator.forward_pair_packed: expected rendered [B,3,H,W] and its packed network input [B,H,W,8]")
+        L.ptr(packed)                                                     # fp32 container, contiguous, on the device
+        ctx.param_at = 3
+        return _train_forward(ctx, module, packed.detach(), (B, 6, H, W), params)
+
+    @staticmethod
+    def backward(ctx, gy):
+        g, param_grads = _train_backward(ctx, gy)
+        dr = split16_to_float(g)[..., :3].permute(0, 3, 1, 2).contiguous() if g is not None else None
+        return (None, dr, None) + param_grads
+
+
+def _check_train_input(module, Cx, H, W):
+    if Cx != module.in_channels or H % 16 or W % 16:
+        raise L.SmirkHipError("SmirkGenerator: expected [B, in_channels, H, W] with H, W multiples of 16")
+    if module.features % 8 or module.in_channels > 8:
+        raise L.SmirkHipError("training runs in the split-fp16 mode: init_features % 8 == 0 and in_channels <= 8")
+
+
+def _train_forward(ctx, module, xin, shape, params):
+    """the forward of the two functions above from the packed network input `xin` [B,H,W,8] on: records the tape on `ctx`"""
+    B, Cx, H, W = shape
+    ctx.arith = getattr(module, "train_arith", "f16x3")
+    ops = _Ops(xin.device, eval_bn=not module.training, arith=ctx.arith)
+    lib, st, f = ops.lib, ops.st, module.features
+    ctx.eval_bn = not module.training
+    plan = getattr(module, "_pack_plan", None)
+    if plan is None or not plan.valid_for(params):                    # first forward (or the parameters were re-allocated): record
+        plan = PackPlan()
+        object.__setattr__(module, "_pack_plan", plan)
+    else:
+        plan.run(ops)                                                 # every conv weight of the network: one launch
+    ops.plan = plan
+    tape = []                                                         # records consumed in reverse by backward()
+
+    def block(seq, tag, x0, x1, h, w, c):
+        m = dict(seq.named_children())
+        c1, n1, c2, n2 = m[tag + "conv1"], m[tag + "norm1"], m[tag + "conv2"], m[tag + "norm2"]
+        c0 = x0.shape[-1]
+        if x1 is None:
+            wf1, wd1a = ops.pack(c1.weight, cin_pad=c0)
+            wd1b = None
+        else:                                                          # decoder: forward weight over cat(up, skip), one data-gradient weight per source
+            wf1, _ = ops.pack(c1.weight, dgrad=False)
+            wd1a = ops.pack(c1.weight, 0, c0, fwd=False)[1]
+            wd1b = ops.pack(c1.weight, c0, x1.shape[-1], fwd=False)[1]
+        z1, st1 = ops.conv_stats(x0, x1, wf1, B, h, w, c)
+        y1, mu1, iv1 = ops.bn_forward(z1, n1, True, stats=st1)
+        wf2, wd2 = ops.pack(c2.weight)
+        z2, st2 = ops.conv_stats(y1, None, wf2, B, h, w, c)
+        y2, mu2, iv2 = ops.bn_forward(z2, n2, True, stats=st2)
+        tape.append(("block", (c1, n1, c2, n2), (x0, x1, z1, mu1, iv1, y1, z2, mu2, iv2, wd1a, wd1b, wd2), (h, w, c)))
+        return y2
+
+    def pool(t, h, w, c):
+        o = torch.empty(B, h // 2, w // 2, c, device=t.device)
+        L.check(lib.smirk_maxpool2x2_split16(L.ptr(t), L.ptr(o), B, h, w, c, st))
+        tape.append(("pool", None, (t,), (h, w, c)))
+        return o
+
+    e1 = block(module.encoder1, "enc1", xin, None, H, W, f)
+    e2 = block(module.encoder2, "enc2", pool(e1, H, W, f), None, H // 2, W // 2, 2 * f)
+    e3 = block(module.encoder3, "enc3", pool(e2, H // 2, W // 2, 2 * f), None, H // 4, W // 4, 4 * f)
+    e4 = block(module.encoder4, "enc4", pool(e3, H // 4, W // 4, 4 * f), None, H // 8, W // 8, 8 * f)
+    h16, w16, c16 = H // 16, W // 16, 16 * f
+    b = block(module.bottleneck, "bottleneck", pool(e4, H // 8, W // 8, 8 * f), None, h16, w16, c16)
+    for rb in module.resnet_blocks:
+        cb = rb.conv_block
+        wfa, wda = ops.pack(cb[1].weight)
+        za, sta = ops.conv_stats(b, None, wfa, B, h16, w16, c16, reflect=True)
+        ya, mua, iva = ops.bn_forward(za, cb[2], True, stats=sta)
+        wfb, wdb = ops.pack(cb[5].weight)
+        zb, stb = ops.conv_stats(ya, None, wfb, B, h16, w16, c16, reflect=True)
+        nb, mub, ivb = ops.bn_forward(zb, cb[6], False, residual=b, stats=stb)
+        tape.append(("res", (cb[1], cb[2], cb[5], cb[6]), (b, za, mua, iva, ya, zb, mub, ivb, wda, wdb), (h16, w16, c16)))
+        b = nb
+    d = b
+    for lvl, skip, div, c in ((4, e4, 16, 8 * f), (3, e3, 8, 4 * f), (2, e2, 4, 2 * f), (1, e1, 2, f)):
+        up = getattr(module, f"upconv{lvl}")
+        wup, wupd = plan.request_special(ops, up.weight, L.PACK_CONVT2X2)   # [Cin, Cout, 2, 2] -> forward 1x1 image, data-gradient image (same launch as every other weight)
+        u = ops.conv(d, None, wup, B, H // div, W // div, c, k=1, convt=True, shift=up.bias.detach().float().contiguous())
+        tape.append(("up", (up,), (d, wupd), (H // div, W // div, 2 * c, c)))
+        d = block(getattr(module, f"decoder{lvl}"), f"dec{lvl}", u, skip, 2 * H // div, 2 * W // div, c)
+    wf = module.conv.weight.detach().float().reshape(module.out_channels, f).contiguous()
+    bf = module.conv.bias.detach().float().contiguous()
+    y = torch.empty(B, module.out_channels, H, W, device=xin.device)
+    L.check(lib.smirk_conv1x1_sigmoid_nchw_split16(L.ptr(d), L.ptr(wf), L.ptr(bf), L.ptr(y), B, H, W, f, module.out_channels, st))
+    if not plan.sealed:
+        plan.seal(params, xin.device)
+    ctx.plan, (ctx.plan_generation, ctx.plan_versions) = plan, plan.stamp(params)
+    ctx.rm_saved = ops.rm_saved
+    ctx.module, ctx.tape, ctx.final = module, tape, (d, wf, y)
+    ctx.shape = (B, Cx, H, W)
+    return y
+
+
+def _train_backward(ctx, gy):
+    """the backward of the two functions above: -> (gradient of the packed network input as split16 [B,H,W,8] or None, the parameters' gradients as a tuple)"""
+    if ctx.tape is None:
+        raise L.second_backward("GeneratorTrainFunction", "raw convolution outputs")
+    module, tape, (d1, wf, y) = ctx.module, ctx.tape, ctx.final
+    B, Cx, H, W = ctx.shape
+    f = module.features
+    ctx.plan.check_tape(ctx.plan_generation, ctx.plan_versions)
+    ops = _Ops(y.device, eval_bn=ctx.eval_bn, arith=ctx.arith)
+    ops.rm_saved = ctx.rm_saved
+    lib, st = ops.lib, ops.st
+    grads = {}                                                        # id(parameter) -> gradient in the parameter's layout
+    # which parameters wanted a gradient WHEN THE FORWARD RAN (smirk_trainer.py:108-113 flips requires_grad off for the eval-mode forward and back on
+    # before backward): a frozen generator pays for data gradients only; in eval mode BatchNorm's affine gradients are not computed at all
+    wanted = {id(p) for p, n in zip(module.parameters(), ctx.needs_input_grad[ctx.param_at:]) if n}
+    if ctx.eval_bn and any(id(bn_p) in wanted for m_ in module.modules() if isinstance(m_, torch.nn.BatchNorm2d) for bn_p in m_.parameters()):
+        raise L.SmirkHipError("eval-mode SmirkGenerator inside autograd: parameter gradients are not implemented (freeze the generator as "
+                              "smirk_trainer.py:108-113 does, or call .train())")
+    need = lambda p: id(p) in wanted
+    want_dx = bool(ctx.needs_input_grad[1])
+    gy = L.as_f32c(gy)
+    # ---- final 1x1 conv + sigmoid ------------------------------------------------------------------------------------------------------
+    dd = torch.empty_like(d1)
+    dl8 = torch.empty(B, H, W, 8, device=y.device)
+    L.check(lib.smirk_conv1x1_sigmoid_backward_split16(L.ptr(gy), L.ptr(y), L.ptr(wf), L.ptr(dd), L.ptr(dl8), B, H, W, f, module.out_channels, st))
+    if need(module.conv.weight):
+        grads[id(module.conv.weight)] = ops.wgrad(dl8, d1, B, H, W, 8, f, 1)[:module.out_channels].reshape(module.out_channels, f, 1, 1)
+    if need(module.conv.bias):
+        grads[id(module.conv.bias)] = ops.colsum(dl8)[:module.out_channels].contiguous()
+
+    def block_backward(rec, g):
+        """g = dL/d(block output) -> (dL/d x0, dL/d x1 or None)"""
+        _, (c1, n1, c2, n2), (x0, x1, z1, mu1, iv1, y1, z2, mu2, iv2, wd1a, wd1b, wd2), (h, w, c) = rec
+        dz2, dg2, db2 = ops.bn_backward(z2, g, n2, mu2, iv2, True)
+        if dg2 is not None:
+            grads[id(n2.weight)], grads[id(n2.bias)] = dg2, db2
+        if need(c2.weight):
+            grads[id(c2.weight)] = ops.wgrad_param(dz2, y1, B, h, w, c, c, 3, _grad_like(c2.weight))
+        dy1 = ops.conv(dz2, None, wd2, B, h, w, c)
+        dz1, dg1, db1 = ops.bn_backward(z1, dy1, n1, mu1, iv1, True)
+        if dg1 is not None:
+            grads[id(n1.weight)], grads[id(n1.bias)] = dg1, db1
+        c0 = x0.shape[-1]
+        if x1 is None:
+            if need(c1.weight):                                       # (the network input is padded 6 -> 8 channels: the two padded ones are dropped)
+                if c1.weight.shape[1] > c0:
+                    raise L.SmirkHipError(f"conv expects {c1.weight.shape[1]} input channels, its source carries {c0}")
+                grads[id(c1.weight)] = ops.wgrad_param(dz1, x0, B, h, w, c, c0, 3, _grad_like(c1.weight), cin_real=c1.weight.shape[1])
+            if rec is tape[0] and not want_dx:                        # the network input needs no gradient (cycle path: it is detached)
+                return None, None
+            return ops.conv(dz1, None, wd1a, B, h, w, c0), None
+        cc1 = x1.shape[-1]
+        if need(c1.weight):                                           # torch.cat((up, skip), 1): channels of source 0 first, both into one tensor
+            if c0 + cc1 != c1.weight.shape[1]:                        # every channel of the parameter must be written by one of the two calls
+                raise L.SmirkHipError(f"decoder conv expects {c1.weight.shape[1]} input channels, its two sources carry {c0} + {cc1}")
+            gw = _grad_like(c1.weight)
+            ops.wgrad_param(dz1, x0, B, h, w, c, c0, 3, gw, cin_off=0)
+            ops.wgrad_param(dz1, x1, B, h, w, c, cc1, 3, gw, cin_off=c0)
+            grads[id(c1.weight)] = gw
+        return ops.conv(dz1, None, wd1a, B, h, w, c0), ops.conv(dz1, None, wd1b, B, h, w, cc1)
+
+    g = dd
+    skip_grad = {}
+    i = len(tape) - 1
+    lvl = 1
+    while i >= 0:
+        rec = tape[i]
+        kind = rec[0]
+        if kind == "block":
+            g0, g1 = block_backward(rec, g)
+            if g1 is not None:                                         # decoder block: x0 = up-sampled tensor, x1 = the encoder's skip tensor
+                skip_grad[lvl] = g1
+                lvl += 1
+            g = g0
+        elif kind == "up":
+            (up,), (xin_, wd), (h, w, cin, cout) = rec[1], rec[2], rec[3]
+            s2d = torch.empty(B, h, w, 4 * cout, device=y.device)
+            L.check(lib.smirk_space_to_depth2_split16(L.ptr(g), L.ptr(s2d), B, h, w, cout, st))
+            if need(up.bias):
+                grads[id(up.bias)] = ops.colsum(g)
+            if need(up.weight):                                        # packed [Cin][(dy,dx,co)] -> the parameter's [Cin][Cout][2][2] in the reduction itself
+                grads[id(up.weight)] = ops.wgrad_param(xin_, s2d, B, h, w, cin, 4 * cout, 1, _grad_like(up.weight), layout=2)
+            g = ops.conv(s2d, None, wd, B, h, w, cin, k=1)
+        elif kind == "res":
+            _, (ca, na, cbv, nbv), (bin_, za, mua, iva, ya, zb, mub, ivb, wda, wdb), (h, w, c) = rec
+            dzb, dgb, dbb = ops.bn_backward(zb, g, nbv, mub, ivb, False)
+            if dgb is not None:
+                grads[id(nbv.weight)], grads[id(nbv.bias)] = dgb, dbb
+            if need(cbv.weight):
+                grads[id(cbv.weight)] = ops.wgrad_param(dzb, ya, B, h, w, c, c, 3, _grad_like(cbv.weight), reflect=True)
+            dpad = ops.conv(dzb, None, wdb, B, h, w, c, pad=2, out_hw=(h + 2, w + 2))
+            dya = torch.empty_like(ya)
+            L.check(lib.smirk_reflect_pad1_backward_split16(L.ptr(dpad), None, L.ptr(dya), B, h, w, c, st))
+            dza, dga, dba = ops.bn_backward(za, dya, na, mua, iva, True)
+            if dga is not None:
+                grads[id(na.weight)], grads[id(na.bias)] = dga, dba
+            if need(ca.weight):
+                grads[id(ca.weight)] = ops.wgrad_param(dza, bin_, B, h, w, c, c, 3, _grad_like(ca.weight), reflect=True)
+            dpad = ops.conv(dza, None, wda, B, h, w, c, pad=2, out_hw=(h + 2, w + 2))
+            gin = torch.empty_like(bin_)
+            L.check(lib.smirk_reflect_pad1_backward_split16(L.ptr(dpad), L.ptr(g), L.ptr(gin), B, h, w, c, st))     # + the identity branch
+            g = gin
+        elif kind == "pool":
+            (t,), (h, w, c) = rec[2], rec[3]
+            level = {f: 1, 2 * f: 2, 4 * f: 3, 8 * f: 4}[c]
+            gx = torch.empty_like(t)
+            L.check(lib.smirk_maxpool2x2_backward_split16(L.ptr(t), L.ptr(g), L.ptr(skip_grad.get(level), allow_none=True), L.ptr(gx), B, h, w, c, st))
+            g = gx
+        i -= 1
+    ctx.tape = ctx.final = None
+    out = []
+    for p in module.parameters():
+        gp = grads.get(id(p))
+        out.append(None if gp is None else gp.reshape(p.shape).to(p.dtype))
+    return (g if want_dx else None), tuple(out)

@@ -272,6 +272,108 @@ class _Replay:
         return self.seed, self.offsets.pop(0)
 
 
+def _hull3(hull_mask, B, H, W):
+    """the hull mask as [B or 1, H, W] fp32, or None where it has another shape"""
+    hull = L.as_f32c(hull_mask)
+    if hull.dim() == 4 and hull.shape[1] == 1:
+        hull = hull[:, 0]
+    if hull.dim() == 3 and hull.shape[0] in (1, B) and tuple(hull.shape[1:]) == (H, W):
+        return hull.contiguous()
+    return None
+
+
+def _train_masked_separate(img, hull_mask, rendered, tv_src, flame_faces, face_probabilities, tv_dst, Ke, mask_ratio, radius, rule, random_mask, rng, S):
+    """the chain smirk_trainer.py:79-92 (tv_dst None) / :262-291 runs, utility by utility: -> (masked, coords with the two point sets)"""
+    B, _, H, W = img.shape
+    points1, coords = mesh_based_mask_uniform_faces(tv_src, flame_faces, face_probabilities, mask_ratio=mask_ratio, IMAGE_SIZE=S, _rng_stream=rng)
+    if tv_dst is None:
+        img_k, p1, points2 = img, points1, points1
+    else:
+        rep = {'sampled_faces_indices': coords['sampled_faces_indices'].repeat(Ke, 1), 'barycentric_coords': coords['barycentric_coords'].repeat(Ke, 1, 1)}
+        points2, _ = mesh_based_mask_uniform_faces(tv_dst, flame_faces, face_probabilities, mask_ratio=mask_ratio, coords=rep, IMAGE_SIZE=S)
+        img_k, p1 = img.repeat(Ke, 1, 1, 1), points1.repeat(Ke, 1, 1)
+    extra = transfer_pixels(img_k, p1, points2)
+    rmask = rendered_mask_of(rendered) if rule == "nonzero" else (rendered > 0).all(dim=1, keepdim=True).float()
+    hull = _hull3(hull_mask, B, H, W)
+    if hull is None:
+        hull = hull_mask if Ke == 1 else hull_mask.repeat(Ke, *([1] * (hull_mask.dim() - 1)))
+    elif hull.shape[0] != 1:                                               # (ONE [1,H,W] mask is broadcast over the Ke * B frames by masking() itself)
+        hull = hull.unsqueeze(1).repeat(Ke, 1, 1, 1)
+    masked = masking(img_k, hull, extra, radius, rendered_mask=rmask, extra_noise=True, random_mask=random_mask, _rng_stream=rng)
+    return masked, dict(coords, points1=points1, points2=points2)
+
+
+def train_masked_image_packed(img, hull_mask, rendered_img, trans_verts_src, flame_faces, face_probabilities, trans_verts_dst=None, Ke=1, mask_ratio=0.01,
+                              mask_dilation_radius=10, rendered_rule="nonzero", random_mask=0.01, rng=None, want_coords=False, image_size=None):
+    """Everything between the renderer and the generator in the trainer's two paths: -> (masked [Ke*B,3,H,W], packed [Ke*B,H,W,8] or None, coords or None).
+    First path (smirk_trainer.py:79-92): trans_verts_dst=None, rendered_rule="nonzero", every sampled pixel is transferred onto itself.  Second path (:262-291):
+    `trans_verts_dst` [Ke*B,V,3] are the vertices of the Ke augmented frames of every source frame, rendered_img [Ke*B,3,H,W] their renderings,
+    rendered_rule="positive", random_mask=0.005.  img [B,3,H,W] and the hull mask ([B,1,H,W], [B,H,W] or one [1,H,W]) are NOT repeated: output frame kb reads
+    frame kb % B.  After the vertex-normal and face-weight launches two launches do the rest (smirk_sample_transfer_points, smirk_train_masking_handoff,
+    include/smirk_train_handoff.h); `packed` is SmirkGenerator.forward_pair_packed's input.  All three results equal bit for bit what the separate utilities
+    (mesh_based_mask_uniform_faces twice, transfer_pixels, the rendered mask, masking, the generator's pack) produce under the same draws: the Philox offsets are
+    allocated in their order - points, field, noise.  `coords` (want_coords=True): 'sampled_faces_indices' and 'barycentric_coords' as
+    mesh_based_mask_uniform_faces returns them, plus 'points1' [B,N,3] and 'points2' [Ke*B,N,3] (the same tensor in the first path).  Points are quantised with
+    `image_size` (default H).  `packed` is None where the fused launches do not serve the call (a radius other than 10, other than 3 channels, random_mask == 0,
+    rows too wide for the LDS band, points quantised for a larger image than this one) or $SMIRK_DISABLE_TRAIN_HANDOFF is set (csrc/switches.h): masked then
+    comes from the separate utilities, under the same draws, and the caller packs as before."""
+    if rendered_rule not in L.RENDERED_RULES:
+        raise ValueError(f"rendered_rule must be one of {L.RENDERED_RULES}")
+    first = trans_verts_dst is None
+    if first and Ke != 1:
+        raise ValueError("Ke > 1 needs trans_verts_dst")
+    img, rendered, tv_src = L.as_f32c(img), L.as_f32c(rendered_img), L.as_f32c(trans_verts_src)
+    tv_dst = None if first else L.as_f32c(trans_verts_dst)
+    B, C, H, W = img.shape
+    KB = Ke * B
+    S = H if image_size is None else int(image_size)
+    n = int(mask_ratio * S * S)
+    hull = _hull3(hull_mask, B, H, W)
+    fused = C == 3 and tuple(rendered.shape) == (KB, 3, H, W) and mask_dilation_radius == 10 and random_mask > 0 and hull is not None and n > 0 \
+        and S <= min(H, W) and not os.environ.get("SMIRK_DISABLE_TRAIN_HANDOFF")
+    separate = lambda stream: _train_masked_separate(img, hull_mask, rendered, tv_src, flame_faces, face_probabilities, tv_dst, Ke, mask_ratio,
+                                                     mask_dilation_radius, rendered_rule, random_mask, stream, S)
+    if not fused:
+        masked, coords = separate(rng)
+        return masked, None, (coords if want_coords else None)
+    lib, st, dev = L.lib(), L.stream_ptr(), img.device
+    mesh, bufs, V, F = _full_mesh(flame_faces)
+    if tuple(tv_src.shape) != (B, V, 3) or not (first or tuple(tv_dst.shape) == (KB, V, 3)):
+        raise L.SmirkHipError("vertex count does not match flame_faces, or frame count does not match img and Ke")
+    normals = torch.empty(B, V, 3, device=dev)
+    L.check(lib.smirk_vertex_normals(mesh, B, L.ptr(tv_src), L.ptr(normals), st))
+    prob = L.as_f32c(face_probabilities.to(dev))
+    wts = torch.empty(B, F, device=dev)
+    L.check(lib.smirk_mask_face_weights(L.ptr(tv_src), L.ptr(normals), L.ptr(bufs['faces'], torch.int32), L.ptr(prob), B, V, F, L.ptr(wts), st))
+    seed, pts_off = _rng(B * n, rng)
+    I32, I64 = torch.int32, torch.int64
+    psrc = torch.empty(B, n, 2, dtype=I32, device=dev)
+    pdst = psrc if first else torch.empty(KB, n, 2, dtype=I32, device=dev)
+    idx = bary = np1 = np2 = None
+    if want_coords:
+        idx, bary, np1 = torch.empty(B, n, dtype=I64, device=dev), torch.empty(B, n, 3, device=dev), torch.empty(B, n, 3, dtype=I64, device=dev)
+        np2 = None if first else torch.empty(KB, n, 3, dtype=I64, device=dev)
+    L.check(lib.smirk_sample_transfer_points(L.ptr(wts), L.ptr(tv_src), L.ptr(tv_dst, allow_none=True), L.ptr(bufs['faces'], I32), B, Ke, V, F, n, S, seed, pts_off,
+                                             L.ptr(psrc, I32), None if first else L.ptr(pdst, I32), L.ptr(idx, I64, True), L.ptr(bary, allow_none=True),
+                                             L.ptr(np1, I64, True), L.ptr(np2, I64, True), st))
+    _, field_off = _rng((KB * H * W + 3) // 4, rng)
+    _, noise_off = _rng(KB * 3 * H * W, rng)
+    masked = torch.empty(KB, 3, H, W, device=dev)
+    packed = torch.empty(KB, H, W, 8, device=dev)
+    code = lib.smirk_train_masking_handoff(L.ptr(img), L.ptr(rendered), L.ptr(hull), H * W if hull.shape[0] == B and B > 1 else 0, L.ptr(psrc, I32),
+                                           L.ptr(pdst, I32), B, Ke, n, H, W, L.RENDERED_RULES.index(rendered_rule), float(random_mask), seed, field_off,
+                                           noise_off, L.ptr(masked), L.ptr(packed), st)
+    if code == L.SMIRK_ERR_UNSUPPORTED:
+        # the same draws through the separate utilities: the three offsets above are the ones they would have allocated
+        masked, coords = separate(_Replay(seed, (pts_off, field_off, noise_off)))
+        return masked, None, (coords if want_coords else None)
+    L.check(code)
+    coords = None
+    if want_coords:
+        coords = {'sampled_faces_indices': idx, 'barycentric_coords': bary, 'points1': np1, 'points2': np1 if first else np2}
+    return masked, packed, coords
+
+
 def demo_masked_image(img, hull_mask, rendered_img, transformed_vertices, flame_faces, face_probabilities,
                       mask_ratio=0.01, mask_ratio_mul=5, mask_dilation_radius=10, rng=None):
     """The block demo.py:138-165 runs between Renderer and SmirkGenerator, on the GPU: rendered mask, mesh-based point sampling with a

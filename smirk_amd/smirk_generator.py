@@ -305,6 +305,29 @@ class SmirkGenerator(nn.Module):
         """generator(torch.cat([rendered, masked], 1)) without materialising the concatenation (smirk_trainer.py:94, demo.py:167)."""
         return self._run(rendered, masked, _taps)
 
+    def accepts_pair_packed(self, rendered):
+        """True where forward_pair_packed serves this module and this `rendered`: split-fp16 arithmetic, the 3 + 3 input channels, and inside autograd (train
+        mode, or eval mode with `rendered` requiring grad)."""
+        return self.precision in SPLIT_PRECISIONS and self.in_channels == 6 and (self.training or (torch.is_grad_enabled() and rendered.requires_grad))
+
+    def forward_pair_packed(self, rendered, packed):
+        """forward_pair(rendered, masked) inside autograd - train mode, or eval mode with `rendered` requiring grad (smirk_trainer.py:94, :108-113, :293) - from
+        the packed split-fp16 network input [B,H,W,8] that masking.train_masked_image_packed wrote: the same autograd function without torch.cat and without the
+        pack launch.  Output, parameter gradients and BatchNorm statistics are the bits of forward_pair; the gradient of `rendered` is channels 0-2 of its input
+        gradient; nothing flows into `packed` (the masked image carries no gradient in the trainer either).  Raises where forward_pair's train path would
+        (precision, in_channels), and in eval mode without an input gradient: that is forward_packed's case."""
+        L.raise_if_range_tripped("smirk_amd.SmirkGenerator.forward_pair_packed")
+        if self.precision not in SPLIT_PRECISIONS or self.in_channels != 6:
+            raise L.SmirkHipError("smirk_amd.SmirkGenerator.forward_pair_packed runs in the split-fp16 ('f16x3') arithmetic mode with in_channels == 6 only "
+                                  "(precision=%r, in_channels=%d)" % (self.precision, self.in_channels))
+        if not self.training and not (torch.is_grad_enabled() and rendered.requires_grad):
+            raise L.SmirkHipError("smirk_amd.SmirkGenerator.forward_pair_packed serves train mode, and eval mode with a `rendered` that requires grad; "
+                                  "gradient-free inference from a packed input is forward_packed")
+        if packed.dim() != 4 or packed.shape[3] != 8:
+            raise L.SmirkHipError("expected the packed network input [B,H,W,8]")
+        from .generator_train import GeneratorTrainPackedFunction
+        return GeneratorTrainPackedFunction.apply(self, rendered, packed.detach(), *self.parameters())
+
     def forward(self, x, _taps=None):
         """x [B,in_channels,H,W] (NCHW, like the reference: cat[rendered_img, masked_img]) -> sigmoid image [B,out,H,W]."""
         return self._run(x, None, _taps)
