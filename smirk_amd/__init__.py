@@ -58,6 +58,8 @@ from . import data  # noqa: E402,F401  (datasets/base_dataset.py:124-215: prepar
 from .data import AugmentConfig, BatchPreparer  # noqa: E402,F401
 from . import visualize  # noqa: E402,F401  (base_trainer.py:130-224: the visualisation sheet, written on the device)
 from .visualize import create_visualizations, save_visualizations  # noqa: E402,F401
+from . import jpeg  # noqa: E402,F401  (base_trainer.py:162 cv2.imwrite, demo_video.py:211-214 cv2.VideoWriter: baseline JPEG files, encoded on the device)
+from .jpeg import JpegBatch, encode_jpeg  # noqa: E402,F401
 
 
 def check_numerics():
@@ -70,4 +72,4 @@ def check_numerics():
 
 __all__ = ["FLAME", "Renderer", "SmirkEncoder", "SmirkGenerator", "SmirkHipError", "lib", "masking", "VideoPipeline", "check_numerics", "TemplateBank", "augment_flame_params",
            "load_templates", "FirstPathLoss", "LossTerms", "weighted_loss", "losses", "first_path", "VGGPerceptualLoss", "MICA", "MappingNetwork", "ExpressionLoss", "Adam",
-           "clip_grad_norm_", "data", "AugmentConfig", "BatchPreparer", "visualize", "create_visualizations", "save_visualizations"]
+           "clip_grad_norm_", "data", "AugmentConfig", "BatchPreparer", "visualize", "create_visualizations", "save_visualizations", "jpeg", "JpegBatch", "encode_jpeg"]

@@ -387,6 +387,20 @@ VISUAL_SIGS = {
 }
 VISUAL_EXPORTS = tuple(VISUAL_SIGS)
 
+# The extension table of include/smirk_jpeg.h (baseline JPEG encoding of uint8 pictures on the device): the same shared object, a version of its own.
+JPEG_ABI_VERSION = 1
+JPEG_HEADER_BYTES, JPEG_MCU_MAX_BYTES, JPEG_MAX_DIM = 629, 1245, 65535      # include/smirk_jpeg.h SMIRK_JPEG_HEADER_BYTES, _MCU_MAX_BYTES, _MAX_DIM
+JpegQuantTables = (C.c_uint8 * 64) * 2
+
+JPEG_SIGS = {
+    "smirk_jpeg_abi_version": (_i, []),
+    "smirk_jpeg_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "smirk_jpeg_max_bytes": (_sz, [_i, _i, _i, _i]),
+    "smirk_jpeg_quant_tables": (_i, [_i, C.POINTER(JpegQuantTables)]),
+    "smirk_jpeg_encode_u8": (_i, [_p, _i, _i, _i, _i, C.POINTER(JpegQuantTables), _i, _p, _sz, _p, _sz, _p, _p]),
+}
+JPEG_EXPORTS = tuple(JPEG_SIGS)
+
 _LIB = None
 
 
@@ -402,14 +416,15 @@ def lib():
             raise SmirkHipError(f"{LIB_PATH} not found: build it with `python -m smirk_amd.build` "
                                 "(smirk_amd has no CPU / eager fallback)")
         L = C.CDLL(LIB_PATH)
-        for table in (_SIGS, MICA_SIGS, EMOTION_SIGS, OPTIM_SIGS, HANDOFF_SIGS, TRAIN_HANDOFF_SIGS, GENPLAN_SIGS, GENARITH_SIGS, DATA_SIGS, VISUAL_SIGS):
+        for table in (_SIGS, MICA_SIGS, EMOTION_SIGS, OPTIM_SIGS, HANDOFF_SIGS, TRAIN_HANDOFF_SIGS, GENPLAN_SIGS, GENARITH_SIGS, DATA_SIGS, VISUAL_SIGS, JPEG_SIGS):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)       # AttributeError => header / library mismatch
                 fn.restype, fn.argtypes = res, args
         if L.smirk_abi_version() != ABI_VERSION or L.smirk_mica_abi_version() != MICA_ABI_VERSION or L.smirk_emotion_abi_version() != EMOTION_ABI_VERSION or \
                 L.smirk_optim_abi_version() != OPTIM_ABI_VERSION or L.smirk_handoff_abi_version() != HANDOFF_ABI_VERSION or \
                 L.smirk_genplan_abi_version() != GENPLAN_ABI_VERSION or L.smirk_genarith_abi_version() != GENARITH_ABI_VERSION or L.smirk_data_abi_version() != DATA_ABI_VERSION or \
-                L.smirk_visual_abi_version() != VISUAL_ABI_VERSION or L.smirk_train_handoff_abi_version() != TRAIN_HANDOFF_ABI_VERSION:
+                L.smirk_visual_abi_version() != VISUAL_ABI_VERSION or L.smirk_train_handoff_abi_version() != TRAIN_HANDOFF_ABI_VERSION or \
+                L.smirk_jpeg_abi_version() != JPEG_ABI_VERSION:
             raise SmirkHipError("libsmirk_hip.so ABI version mismatch; rebuild")
         _LIB = L
     return _LIB

@@ -46,7 +46,7 @@ def build(force=False, verbose=True):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(LIBDIR, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    headers += [os.path.join(os.path.dirname(HERE), "include", f) for f in ("smirk_hip.h", "smirk_mica.h", "smirk_emotion.h", "smirk_optim.h", "smirk_handoff.h", "smirk_train_handoff.h", "smirk_generator_plan.h", "smirk_generator_arith.h", "smirk_data.h", "smirk_visual.h")]
+    headers += [os.path.join(os.path.dirname(HERE), "include", f) for f in ("smirk_hip.h", "smirk_mica.h", "smirk_emotion.h", "smirk_optim.h", "smirk_handoff.h", "smirk_train_handoff.h", "smirk_generator_plan.h", "smirk_generator_arith.h", "smirk_data.h", "smirk_visual.h", "smirk_jpeg.h")]
     objs, jobs = [], []
     for s in sources():
         src = os.path.join(CSRC, s)

@@ -10,8 +10,11 @@ cv2 encode.  Here N decoded frames are staged in pinned host memory, uploaded on
 
 Decoding, the mediapipe landmark detector and encoding stay with the caller (third-party CPU components, out of scope): `run()` takes an
 iterable of frames and an iterable of landmark arrays (what utils/mediapipe_utils.run_mediapipe returns) and yields output frames.
+`run(..., jpeg=dict(quality=95))` is the opt-in alternative for the last step: the grids are encoded on the compute stream (smirk_amd.jpeg), only the files'
+bytes are downloaded, and MjpegWriter below puts them into a Motion-JPEG AVI.
 """
 import collections
+import struct
 
 import numpy as np
 import torch
@@ -63,6 +66,7 @@ class VideoPipeline:
         self.depth = max(1, int(depth))
         self._slots = [_Slot() for _ in range(self.depth)]
         self._in_stream = self._out_stream = None
+        self._jpeg = None
 
     # ---- buffers -----------------------------------------------------------------------------------------------------------------
     def _prepare(self, slot, Hv, Wv, L_pts):
@@ -124,10 +128,14 @@ class VideoPipeline:
             slot.ev_in.record(self._in_stream)
         cur.wait_event(slot.ev_in)
         self._compute(slot, Hv, Wv, L_pts)
+        if self._jpeg is not None:                              # on the compute stream: only the files' bytes are downloaded, in _drain
+            from .jpeg import encode_jpeg
+            slot.jpeg = encode_jpeg(slot.d_grid, bgr=True, **self._jpeg)
         slot.ev_done.record(cur)
         with torch.cuda.stream(self._out_stream):
             self._out_stream.wait_event(slot.ev_done)
-            slot.h_grid.copy_(slot.d_grid, non_blocking=True)
+            if self._jpeg is None:
+                slot.h_grid.copy_(slot.d_grid, non_blocking=True)
             slot.ev_out.record(self._out_stream)
         slot.n, slot.used = n, True
 
@@ -170,15 +178,24 @@ class VideoPipeline:
             L.check(lib.smirk_f32_nchw_to_u8_grid(P(big), N, Hv, Wv, 1, P(slot.d_grid, U8), gw, j * Wo, st))
 
     def _drain(self, slot):
+        if self._jpeg is not None:                              # the copy-out stream already waits for the slot's encode
+            files, slot.jpeg = slot.jpeg.to_host(stream=self._out_stream), None
+            yield from files[:slot.n]
+            return
         slot.ev_out.synchronize()
         g = slot.h_grid.numpy()
         for i in range(slot.n):
             yield g[i].copy()
 
     # ---- the stream ----------------------------------------------------------------------------------------------------------------
-    def run(self, frames, landmarks=None):
+    def run(self, frames, landmarks=None, jpeg=None):
         """frames: iterable of uint8 [H,W,3] BGR arrays (cv2.VideoCapture.read order); landmarks: parallel iterable of [L,>=2] arrays or
-        None entries (run_mediapipe's result per frame).  Yields one uint8 BGR grid per input frame, in order."""
+        None entries (run_mediapipe's result per frame).  Yields one uint8 BGR grid per input frame, in order.
+        jpeg: None, or the keyword arguments of smirk_amd.encode_jpeg other than bgr (dict(quality=95), restart_interval): every grid is encoded on the compute
+        stream and one `bytes` (a complete JFIF file, what MjpegWriter.write takes) is yielded per frame instead of the array."""
+        if jpeg is not None and not set(jpeg) <= {"quality", "restart_interval"}:
+            raise ValueError(f"VideoPipeline.run: jpeg takes quality and restart_interval, got {sorted(jpeg)}")
+        self._jpeg = None if jpeg is None else dict(jpeg)
         if self._in_stream is None:
             self._in_stream, self._out_stream = torch.cuda.Stream(device=self.device), torch.cuda.Stream(device=self.device)
         lm_iter = iter(landmarks) if landmarks is not None else None
@@ -208,3 +225,60 @@ class VideoPipeline:
                 flush_batch()
             while pending:
                 yield from self._drain(pending.popleft())
+
+
+class MjpegWriter:
+    """Motion-JPEG in a RIFF/AVI container, pure Python: what cv2.VideoWriter(path, fourcc('MJPG'), fps, (width, height)) is to demo_video.py:211-214, for frames
+    that are already JPEG files (VideoPipeline.run(..., jpeg=...)).
+
+        with MjpegWriter("out.avi", fps, width, height) as w:
+            for data in vp.run(frames, landmarks, jpeg=dict(quality=95)):
+                w.write(data)
+
+    One video stream `MJPG`, every frame a `00dc` chunk (a key frame) inside LIST movi, then the `idx1` index; the frame count and the sizes are patched on close()."""
+
+    def __init__(self, path, fps, width, height):
+        fps = float(fps)
+        if not fps > 0 or int(width) < 1 or int(height) < 1:
+            raise ValueError("MjpegWriter: fps, width and height must be positive")
+        self.width, self.height = int(width), int(height)
+        self.rate, self.scale = (int(round(fps * 1000)), 1000) if fps != int(fps) else (int(fps), 1)
+        self.index, self.largest, self.f = [], 0, open(path, "wb")
+        self.f.write(self._headers(0, 0, 0))
+        self.movi = self.f.tell() - 4                            # position of the 'movi' fourcc: idx1 offsets count from here
+
+    def _headers(self, frames, movi_bytes, riff_bytes):
+        usec = int(round(1e6 * self.scale / self.rate))
+        avih = struct.pack("<14I", usec, self.largest * self.rate // self.scale, 0, 0x10, frames, 0, 1, self.largest, self.width, self.height, 0, 0, 0, 0)     # 0x10: AVIF_HASINDEX
+        strh = struct.pack("<4s4sIHHIIIIIIIIhhhh", b"vids", b"MJPG", 0, 0, 0, 0, self.scale, self.rate, 0, frames, self.largest, 0xFFFFFFFF, 0, 0, 0, self.width,
+                           self.height)
+        strf = struct.pack("<IiiHH4sIiiII", 40, self.width, self.height, 1, 24, b"MJPG", self.width * self.height * 3, 0, 0, 0, 0)
+        strl = b"strl" + b"strh" + struct.pack("<I", len(strh)) + strh + b"strf" + struct.pack("<I", len(strf)) + strf
+        hdrl = b"hdrl" + b"avih" + struct.pack("<I", len(avih)) + avih + b"LIST" + struct.pack("<I", len(strl)) + strl
+        return b"RIFF" + struct.pack("<I", riff_bytes) + b"AVI " + b"LIST" + struct.pack("<I", len(hdrl)) + hdrl + b"LIST" + struct.pack("<I", movi_bytes) + b"movi"
+
+    def write(self, data):
+        data = bytes(data)
+        if self.f is None:
+            raise ValueError("MjpegWriter: write after close")
+        self.index.append((self.f.tell() - self.movi, len(data)))
+        self.f.write(b"00dc" + struct.pack("<I", len(data)) + data + (b"\0" if len(data) & 1 else b""))
+        self.largest = max(self.largest, len(data))
+
+    def close(self):
+        if self.f is None:
+            return
+        movi_bytes = self.f.tell() - self.movi
+        idx = b"".join(struct.pack("<4sIII", b"00dc", 0x10, off, n) for off, n in self.index)                   # 0x10: AVIIF_KEYFRAME
+        self.f.write(b"idx1" + struct.pack("<I", len(idx)) + idx)
+        riff_bytes = self.f.tell() - 8
+        self.f.seek(0)
+        self.f.write(self._headers(len(self.index), movi_bytes, riff_bytes))
+        self.f.close()
+        self.f = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

@@ -192,10 +192,24 @@ def download_sheet(sheet, H, W):
     return host.numpy()[:H * W * 3].reshape(H, W, 3)
 
 
-def save_visualizations(visualizations, save_path=None, show_landmarks=False, Ke=1, bgr=True):
+def save_visualizations(visualizations, save_path=None, show_landmarks=False, Ke=1, bgr=True, encoder=None, return_sheet=True, quality=None):
     """base_trainer.py:130-162.  -> the sheet, uint8 [H, W, 3], BGR (what the reference hands to cv2.imwrite) or RGB with bgr=False; an array of its own, not the
-    pinned buffer.  With `save_path` the file is written with PIL (ImportError where it is absent); encoding stays on the host.  CPU tensors raise SmirkHipError."""
+    pinned buffer.  With `save_path` the file is written with PIL (ImportError where it is absent); encoding stays on the host.  CPU tensors raise SmirkHipError.
+    encoder="hip" with a .jpg / .jpeg path encodes the sheet on the device instead (smirk_amd.jpeg, `quality` default 95 like cv2.imwrite): only the file's bytes are
+    downloaded and written, and return_sheet=False skips the download of the sheet itself (-> None)."""
+    if encoder not in (None, "hip"):
+        raise ValueError(f"save_visualizations: encoder must be None (PIL on the host) or 'hip', got {encoder!r}")
+    if encoder == "hip" and (save_path is None or not str(save_path).lower().endswith((".jpg", ".jpeg"))):
+        raise ValueError("save_visualizations: encoder='hip' writes JPEG files: save_path must end in .jpg or .jpeg")
+    if encoder is None and (quality is not None or not return_sheet):
+        raise ValueError("save_visualizations: quality and return_sheet=False belong to encoder='hip'")
     sheet, H, W = render_sheet(visualizations, show_landmarks, Ke, bgr)
+    if encoder == "hip":
+        from .jpeg import DEFAULT_QUALITY, encode_jpeg
+        data = encode_jpeg(sheet[:H * W * 3].view(1, H, W, 3), DEFAULT_QUALITY if quality is None else quality, bgr=bgr).to_host()[0]
+        with open(save_path, "wb") as f:
+            f.write(data)
+        return download_sheet(sheet, H, W).copy() if return_sheet else None
     out = download_sheet(sheet, H, W).copy()
     if save_path is not None:
         from PIL import Image
